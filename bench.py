@@ -25,7 +25,13 @@ C4).  value = (payload bytes S_pad of all segments of all ranks, all steps) /
 t_decode) aggregated; the total is fixed, so scaling is "strong".
 
 Run: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
-torch.distributed.run (one process per GPU).
+torch.distributed.run (one process per GPU).  Such a plain run sets up, warms
+up, times the K steps and prints the result line (value, ms_per_step, the
+per-launch times of the timed steps).  --full adds, after the timed steps, the
+checks (round trip, oracle) and every other leg: the warm shared-set decode,
+the parity-only encode, the no-arithmetic schedule and streaming ceilings, the
+fresh-share-set legs, the other configurations, the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 from __future__ import annotations
 
@@ -71,9 +77,17 @@ def parse():
                     help="BASELINE configs[3]: segments per step over all ranks (sharded contiguously)")
     ap.add_argument("--batch", type=int, default=32,
                     help="segments per launch (32: +1.3 %% over 16, the rebuild's grid twice as long; DESIGN.md §5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the bench reports: the correctness checks "
+                         "(round trip, oracle), the warm shared-set decode, the parity-only encode, the no-arithmetic "
+                         "schedule and streaming ceilings, the fresh-share-set legs, the other configurations and the "
+                         "CPU baseline.  Without it: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step's launches left in the pieces and rebuilt "
+                         "segments buffers as DIR/<name>.npy (dump_outputs: per-buffer byte sums and a seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the RS(20,50)/(30,60)/(50,80) entries (PMC passes: only RS(29,80) launches)")
+                    help="with --full: skip the RS(20,50)/(30,60)/(50,80) entries (PMC passes: only RS(29,80) launches)")
     ap.add_argument("--cpu-sample-s", type=float, default=10.0,
                     help="CPU baseline: seconds of reference-shaped work on all host cores (plus shorter single-core "
                          "and optimised-variant samples)")
@@ -586,6 +600,50 @@ def warm_shared_set_leg(L, ctx, encode, pieces, outs, segs, pool, B, dev, stream
             "verified": ok, "note": "informational, not in value (uplink's downloads do not reuse sets)"}
 
 
+def dump_offsets(plen: int, slen: int, rows: int, npieces: int = N):
+    """The byte offsets dump_outputs samples in every piece (of plen bytes)
+    and every rebuilt segment (of slen bytes): sorted, seeded, the same in
+    every run; as many as keep `rows` segments' samples within 48 MB."""
+    rows = max(rows, 1)
+    n_p = max(1, min(1024, plen, (40 << 20) // (4 * rows * npieces)))
+    n_s = max(1, min(16384, slen, (8 << 20) // (4 * rows)))
+    rng = np.random.default_rng(0x0D0C5)
+    return np.sort(rng.choice(plen, n_p, replace=False)), np.sort(rng.choice(slen, n_s, replace=False))
+
+
+def dump_outputs(out_dir, launches, pool, pieces, outs, suffix=""):
+    """What the last timed step left for its caller, as float .npy files under
+    out_dir: a step's launches cycle over the pool's slots, so after it every
+    slot a launch used holds that slot's last launch -- nb segments' 80 pieces
+    (ec_encode_segments) and the nb segments rebuilt from them
+    (ec_rebuild_segments_sets).  The buffers are GBs, so per slot:
+      pieces_bytesum_slot<s>   float64 (nb, 80): the sum of each piece's bytes (exact)
+      pieces_sample_slot<s>    float32 (nb, 80, P): each piece's bytes at P fixed seeded offsets
+      rebuilt_bytesum_slot<s>  float64 (nb,): the sum of each rebuilt segment's bytes
+      rebuilt_sample_slot<s>   float32 (nb, S): each rebuilt segment's bytes at S fixed seeded offsets
+    P and S (1024 and 16384 at the default batch) keep the files under 64 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    last = {}
+    for b, nb in enumerate(launches):
+        last[b % pool] = nb
+    dev = pieces[0].device
+    p_off, s_off = (torch.from_numpy(x).to(dev) for x in dump_offsets(
+        pieces[0].shape[2], outs[0].shape[1], sum(last.values()), pieces[0].shape[1]))
+    for slot, nb in sorted(last.items()):
+        arrays = {  # (one segment at a time: small index and reduction launches)
+            f"pieces_bytesum_slot{slot}": torch.stack(
+                [pieces[slot][g].sum(dim=1, dtype=torch.int64) for g in range(nb)]).to(torch.float64),
+            f"pieces_sample_slot{slot}": torch.stack(
+                [torch.index_select(pieces[slot][g], 1, p_off) for g in range(nb)]).to(torch.float32),
+            f"rebuilt_bytesum_slot{slot}": torch.stack(
+                [outs[slot][g].sum(dtype=torch.int64) for g in range(nb)]).to(torch.float64),
+            f"rebuilt_sample_slot{slot}": torch.stack(
+                [torch.index_select(outs[slot][g], 0, s_off) for g in range(nb)]).to(torch.float32),
+        }
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.cpu().numpy())
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -641,10 +699,13 @@ def main():
         """one call's arrays, made before the timed region (a Go caller holds its slices)"""
         n = len(sets_)
         flat = [x for st in sets_ for x in st]
+        # (addresses from the slot's base: indexing the tensors once per share costs a plain run
+        # ~0.1 s per step of set-up)
+        p0, o0 = pieces[slot].data_ptr(), outs[slot].data_ptr()
         return (n, (ctypes.c_int * n)(*[K] * n), (ctypes.c_int * len(flat))(*flat),
-                (ctypes.c_void_p * len(flat))(*[pieces[slot][g].data_ptr() + x * PIECE
+                (ctypes.c_void_p * len(flat))(*[p0 + (g * N + x) * PIECE
                                                 for g, st in enumerate(sets_) for x in st]),
-                (ctypes.c_void_p * n)(*[outs[slot][g].data_ptr() for g in range(n)]), sets_)
+                (ctypes.c_void_p * n)(*[o0 + g * S_PAD for g in range(n)]), sets_)
 
     def decode(slot, a):
         n, nsh, nums, ptrs, optr, _ = a
@@ -736,29 +797,36 @@ def main():
         ranks_seen = int(seen.item())
         wall = max(rank_walls)
 
-    # correctness (outside the timed region): every pool slot's segments encoded and rebuilt from
-    # fresh share sets (one segment all parity) equal their input, and one segment's pieces match
-    # the oracle
-    verified = True
-    for slot in range(pool):
-        outs[slot].zero_()
-        encode(slot, B)
-        decode(slot, fresh_args(slot, B, True))
-        torch.cuda.synchronize(dev)
-        verified = verified and bool(torch.equal(outs[slot], segs[slot]))
-    verified = verified and oracle_spot_check(pieces[0][0], segs[0][0])
+    # --dump-outputs: what the last timed step left in the buffers, before anything else writes them
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, launches, pool, pieces, outs, f"_rank{rank}" if world > 1 else "")
 
-    # informational, outside the timed region: the same decode from ONE warm share set per launch
-    # (ec_rebuild_segments_batched, the set's straight-line code made and waited for before
-    # timing) -- what a caller reusing a set gets; uplink's downloads do not (the timed leg)
-    warm = warm_shared_set_leg(L, ctx, encode, pieces, outs, segs, pool, B, dev, stream, sptr)
+    # a plain run ends here, with the line of the timed steps; the rest only with --full
+    verified = warm = par = None
+    if args.full:
+        # correctness (outside the timed region): every pool slot's segments encoded and rebuilt from
+        # fresh share sets (one segment all parity) equal their input, and one segment's pieces match
+        # the oracle
+        verified = True
+        for slot in range(pool):
+            outs[slot].zero_()
+            encode(slot, B)
+            decode(slot, fresh_args(slot, B, True))
+            torch.cuda.synchronize(dev)
+            verified = verified and bool(torch.equal(outs[slot], segs[slot]))
+        verified = verified and oracle_spot_check(pieces[0][0], segs[0][0])
 
-    # informational, outside the timed region: the parity-only encode (data pieces are the
-    # segment's own shares, served in place; the upload path of §8f row 1 uses this form), and
-    # the encoder's own schedule without arithmetic (ec_encode_shape_probe, both forms).  Timed
-    # like the headline encode -- each launch followed by a decode launch, per-launch events --
-    # and also back to back, where a denser VALU body runs at a lower sustained clock.
-    par = torch.empty((B, N - K, PIECE), dtype=torch.uint8, device=dev)
+        # informational, outside the timed region: the same decode from ONE warm share set per launch
+        # (ec_rebuild_segments_batched, the set's straight-line code made and waited for before
+        # timing) -- what a caller reusing a set gets; uplink's downloads do not (the timed leg)
+        warm = warm_shared_set_leg(L, ctx, encode, pieces, outs, segs, pool, B, dev, stream, sptr)
+
+        # informational, outside the timed region: the parity-only encode (data pieces are the
+        # segment's own shares, served in place; the upload path of §8f row 1 uses this form), and
+        # the encoder's own schedule without arithmetic (ec_encode_shape_probe, both forms).  Timed
+        # like the headline encode -- each launch followed by a decode launch, per-launch events --
+        # and also back to back, where a denser VALU body runs at a lower sustained clock.
+        par = torch.empty((B, N - K, PIECE), dtype=torch.uint8, device=dev)
 
     def par_encode():
         if L.ec_encode_segments(ctx, segs[0].data_ptr(), B, NSTRIPES, par.data_ptr(), _native.EC_FLAG_PARITY_ONLY,
@@ -801,23 +869,24 @@ def main():
         pe[1].synchronize()
         return (sum(a.elapsed_time(b) for a, b in pev) / reps * 1e-3, pe[0].elapsed_time(pe[1]) / reps * 1e-3)
 
-    t_par, t_par_b2b = timed_like_headline(par_encode)
-    encode(0, B)
-    torch.cuda.synchronize(dev)
-    verified = verified and bool(torch.equal(par, pieces[0][:, K:]))
-    shape_ok = hasattr(L, "ec_encode_shape_probe")
-    t_shape = t_shape_b2b = t_shape_par = t_shape_par_b2b = None
-    if shape_ok:
-        t_shape, t_shape_b2b = timed_like_headline(shape_full)
-        t_shape_par, t_shape_par_b2b = timed_like_headline(shape_par)
-        encode(0, B)  # (pieces[0] holds the probe's copies: the real pieces again)
+    shape_ok = args.full and hasattr(L, "ec_encode_shape_probe")
+    t_par = t_par_b2b = t_shape = t_shape_b2b = t_shape_par = t_shape_par_b2b = None
+    if args.full:
+        t_par, t_par_b2b = timed_like_headline(par_encode)
+        encode(0, B)
         torch.cuda.synchronize(dev)
-    del par
-    if use_dist:
-        import torch.distributed as dist
-        v = torch.tensor([1 if verified else 0], device=coll_dev or dev)
-        dist.all_reduce(v, op=dist.ReduceOp.MIN)
-        verified = bool(v.item())
+        verified = verified and bool(torch.equal(par, pieces[0][:, K:]))
+        if shape_ok:
+            t_shape, t_shape_b2b = timed_like_headline(shape_full)
+            t_shape_par, t_shape_par_b2b = timed_like_headline(shape_par)
+            encode(0, B)  # (pieces[0] holds the probe's copies: the real pieces again)
+            torch.cuda.synchronize(dev)
+        del par
+        if use_dist:
+            import torch.distributed as dist
+            v = torch.tensor([1 if verified else 0], device=coll_dev or dev)
+            dist.all_reduce(v, op=dist.ReduceOp.MIN)
+            verified = bool(v.item())
 
     total_payload = args.steps * args.total_segments * S_PAD
     value = total_payload / 2**30 / wall
@@ -836,16 +905,17 @@ def main():
                    "bytes_per_launch": int(dec_bytes), "achieved_GBps": round(dec_gbps, 1),
                    "rows_per_segment": (f"{rows_timed[0]}..{rows_timed[-1]} (median {rows_timed[len(rows_timed) // 2]})"
                                         if rows_timed else None)},
-        "decode_warm_shared_set": warm,
     }
     par_bytes = B * S_PAD * (1 + (N - K) / K)
-    par_frac = round(par_bytes / t_par / 1e9 / HBM_PEAK_GBPS, 4)
-    kernels["encode_parity_only"] = {
-        "kernel": (ENC_PARITY_KERNEL if enc_name == "special" else "rs_matmul_dma<7, 1>")
-                  + " (EC_FLAG_PARITY_ONLY)", "avg_us": round(t_par * 1e6, 2),
-        "avg_us_back_to_back": round(t_par_b2b * 1e6, 2),
-        "bytes_per_launch": int(par_bytes), "achieved_GBps": round(par_bytes / t_par / 1e9, 1),
-        "frac": par_frac, "note": "informational, not in value"}
+    if args.full:
+        kernels["decode_warm_shared_set"] = warm
+        par_frac = round(par_bytes / t_par / 1e9 / HBM_PEAK_GBPS, 4)
+        kernels["encode_parity_only"] = {
+            "kernel": (ENC_PARITY_KERNEL if enc_name == "special" else "rs_matmul_dma<7, 1>")
+                      + " (EC_FLAG_PARITY_ONLY)", "avg_us": round(t_par * 1e6, 2),
+            "avg_us_back_to_back": round(t_par_b2b * 1e6, 2),
+            "bytes_per_launch": int(par_bytes), "achieved_GBps": round(par_bytes / t_par / 1e9, 1),
+            "frac": par_frac, "note": "informational, not in value"}
     shape_gbps = enc_bytes / t_shape / 1e9 if t_shape else None
     shape_par_gbps = par_bytes / t_shape_par / 1e9 if t_shape_par else None
     if shape_ok:
@@ -862,7 +932,7 @@ def main():
     # SURVEY §8d, VERDICT r4 item 4: on-box ceilings next to the spec peak -- the library's own
     # streaming kernels (ec_bw_probe, no arithmetic) in the read:write mixes of the kernels measured
     # here, in the best shapes of the round-2 probes; outside the timed region
-    ceil = on_box_ceilings(L, dev, stream) if hasattr(L, "ec_bw_probe") else {}
+    ceil = on_box_ceilings(L, dev, stream) if args.full and hasattr(L, "ec_bw_probe") else {}
     dominant = "encode" if t_enc_full >= t_dec_full else "decode"
     dk = kernels[dominant]
     # PMC traffic of the dominant kernel, from the record tools/prof_round.sh wrote for one build:
@@ -903,24 +973,8 @@ def main():
                    "parallelism": f"segments sharded over {world} GPU(s), no collective"},
         "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(dk["achieved_GBps"], 1),
                      "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(dk["achieved_GBps"] / HBM_PEAK_GBPS, 4),
-                     "traffic": traffic, "traffic_note": traffic_note, "frac_parity_only_encode": par_frac,
-                     "frac_decode": round(dec_gbps / HBM_PEAK_GBPS, 4),
-                     "copy_GBps_on_box": _r(ceil.get("copy"), 1),
-                     "encode_mix_GBps_on_box": _r(ceil.get("encode_mix"), 1),
-                     "parity_mix_GBps_on_box": _r(ceil.get("parity_mix"), 1),
-                     "frac_of_mix": _ratio(enc_gbps, ceil.get("encode_mix")),
-                     "frac_of_mix_parity_only": _ratio(par_bytes / t_par / 1e9, ceil.get("parity_mix")),
-                     "frac_decode_of_copy": _ratio(dec_gbps, ceil.get("copy")),
-                     "encode_shape_GBps_on_box": _r(shape_gbps, 1),
-                     "parity_shape_GBps_on_box": _r(shape_par_gbps, 1),
-                     "frac_of_shape": _ratio(enc_gbps, shape_gbps),
-                     "frac_of_shape_parity_only": _ratio(par_bytes / t_par / 1e9, shape_par_gbps),
-                     "shape_frac_of_peak": _ratio(shape_gbps, HBM_PEAK_GBPS),
-                     "ceilings_note": "ec_bw_probe: one-shot grid, each wave R KiB in / W KiB out, 16 B per lane, "
-                                      "non-temporal, no arithmetic; copy 1:1, encode mix 4:11 (the encode's 29:80), "
-                                      "parity mix 4:7 (29:51); 1 GiB read, median of 10 launches; encode shape: "
-                                      "the encoder's own schedule without arithmetic (ec_encode_shape_probe), timed "
-                                      "as the encode is"},
+                     "traffic": traffic, "traffic_note": traffic_note,
+                     "frac_decode": round(dec_gbps / HBM_PEAK_GBPS, 4)},
         "kernels": kernels,
         "encode_gibps": round(B * S_PAD / 2**30 / t_enc_full, 2),
         "decode_gibps": round(B * S_PAD / 2**30 / t_dec_full, 2),
@@ -930,25 +984,45 @@ def main():
         "collectives": backend if use_dist else None,
         "rank_wall_s": rank_walls,
         "build_id": L.ec_build_id().decode(),
-        "verified": verified,
+        "full": args.full,
     }
-    # after the timed region, on rank 0 at every world size: the decode with a
-    # fresh share set per segment, the reference benchmark's other configurations, the CPU baseline
-    if rank == 0 and hasattr(L, "ec_rebuild_segments_sets"):  # (an older --lib build lacks it)
-        line["fresh_share_sets"] = fresh_sets_leg(L, ctx, dev, sptr)
-    if rank == 0 and not args.no_other_configs:
-        line["other_configs"] = other_configs(L, dev, sptr)
-        for key, val in line.get("fresh_share_sets", {}).items():  # (VERDICT r4 item 1 asks for them here too)
-            if key != "note":
-                line["other_configs"][f"RS(29,80) rebuild, {key}"] = val
-        line["other_configs"]["RS(29,80) rebuild, a new share set every launch"] = fresh_share_sets(L, dev, sptr)
-        if hasattr(L, "ec_decode_segments_batched"):
-            line["other_configs"]["RS(29,80) decode with error detection"] = decode_with_detection(L, dev, sptr)
-    if rank == 0 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(args.cpu_sample_s)
-    if use_dist:  # the other ranks wait for rank 0's informational legs
-        import torch.distributed as dist
-        dist.barrier()
+    if args.full:
+        line["verified"] = verified
+        line["roofline"].update({
+            "frac_parity_only_encode": par_frac,
+            "copy_GBps_on_box": _r(ceil.get("copy"), 1),
+            "encode_mix_GBps_on_box": _r(ceil.get("encode_mix"), 1),
+            "parity_mix_GBps_on_box": _r(ceil.get("parity_mix"), 1),
+            "frac_of_mix": _ratio(enc_gbps, ceil.get("encode_mix")),
+            "frac_of_mix_parity_only": _ratio(par_bytes / t_par / 1e9, ceil.get("parity_mix")),
+            "frac_decode_of_copy": _ratio(dec_gbps, ceil.get("copy")),
+            "encode_shape_GBps_on_box": _r(shape_gbps, 1),
+            "parity_shape_GBps_on_box": _r(shape_par_gbps, 1),
+            "frac_of_shape": _ratio(enc_gbps, shape_gbps),
+            "frac_of_shape_parity_only": _ratio(par_bytes / t_par / 1e9, shape_par_gbps),
+            "shape_frac_of_peak": _ratio(shape_gbps, HBM_PEAK_GBPS),
+            "ceilings_note": "ec_bw_probe: one-shot grid, each wave R KiB in / W KiB out, 16 B per lane, "
+                             "non-temporal, no arithmetic; copy 1:1, encode mix 4:11 (the encode's 29:80), "
+                             "parity mix 4:7 (29:51); 1 GiB read, median of 10 launches; encode shape: "
+                             "the encoder's own schedule without arithmetic (ec_encode_shape_probe), timed "
+                             "as the encode is"})
+        # after the timed region, on rank 0 at every world size: the decode with a
+        # fresh share set per segment, the reference benchmark's other configurations, the CPU baseline
+        if rank == 0 and hasattr(L, "ec_rebuild_segments_sets"):  # (an older --lib build lacks it)
+            line["fresh_share_sets"] = fresh_sets_leg(L, ctx, dev, sptr)
+        if rank == 0 and not args.no_other_configs:
+            line["other_configs"] = other_configs(L, dev, sptr)
+            for key, val in line.get("fresh_share_sets", {}).items():  # (VERDICT r4 item 1 asks for them here too)
+                if key != "note":
+                    line["other_configs"][f"RS(29,80) rebuild, {key}"] = val
+            line["other_configs"]["RS(29,80) rebuild, a new share set every launch"] = fresh_share_sets(L, dev, sptr)
+            if hasattr(L, "ec_decode_segments_batched"):
+                line["other_configs"]["RS(29,80) decode with error detection"] = decode_with_detection(L, dev, sptr)
+        if rank == 0 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(args.cpu_sample_s)
+        if use_dist:  # the other ranks wait for rank 0's informational legs
+            import torch.distributed as dist
+            dist.barrier()
     if rank == 0:
         print(json.dumps(line), flush=True)
     L.ec_destroy(ctx)

@@ -5,7 +5,7 @@ O=$1; shift
 mkdir -p $O
 for i in 1 2; do
   for B in "$@"; do
-    timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs --batch $B > $O/b${B}_$i.log 2>&1
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs --batch $B > $O/b${B}_$i.log 2>&1
   done
 done
 echo done

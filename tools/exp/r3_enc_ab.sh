@@ -9,7 +9,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --ti
 for i in 1 2; do
   n=0
   for L in "$@"; do
-    timeout -k 10 200 python bench.py --no-cpu-baseline --no-other-configs --lib $L > $O/v${n}_$i.log 2>&1
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-other-configs --lib $L > $O/v${n}_$i.log 2>&1
     n=$((n+1))
   done
 done

@@ -58,7 +58,7 @@ from uplink_amd import _native  # noqa: E402  (the build the passes ran: bench.p
 res = {
     "build_id": _native.load().ec_build_id().decode(),
     "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace) of `python3 bench.py "
-              f"--steps 3 --warmup 1 --settle-s 0 --no-cpu-baseline --no-other-configs` ({B} RS(29,80) 64 MiB segments per launch); mean "
+              f"--full --steps 3 --warmup 1 --settle-s 0 --no-cpu-baseline --no-other-configs` ({B} RS(29,80) 64 MiB segments per launch); mean "
               "over dispatches; FETCH_SIZE doubled per MI355X_MICROARCH.md §HBM; tools/pmc_traffic.py",
     "segments_per_launch": B,
     "encode": family("rs_encode_special<29, 80, 8, 4, true>"),
