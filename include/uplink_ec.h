@@ -27,6 +27,11 @@
  *                            StripeReader.ReadStripes  stripe.go:382-428
  *   ec_*_segments_sets       the same for many segments with a share set each:
  *                            one StripeReader per download, ecclient/client.go:273-308
+ *   ec_repair_segments_sets  segment repair: the lost pieces regenerated from any k, a
+ *                            share set per segment -- what the repair and graceful-exit
+ *                            callers of ecclient.Client do with Get + PutSingleResult /
+ *                            PutPiece (ecclient/client.go:36-44,77-101), without the
+ *                            decoded segment in between
  *   ec_*_segments_host       the same batches from/to host memory (PCIe pipeline)
  *   ec_*blake3* / ec_hash_segments / ec_encode_segments_host_hashed
  *                            BLAKE3 piece hash of the upload (piecestore/upload.go:
@@ -77,6 +82,7 @@ extern "C" {
 /* flags for ec_encode_segments */
 #define EC_FLAG_PARITY_ONLY 0x1 /* write only the n-k parity pieces */
 #define EC_FLAG_HASH_PIECES 0x2 /* ec_upload_begin: also the BLAKE3 of every piece (ec_upload_hashes) */
+#define EC_FLAG_CHECK_SHARES 0x4 /* ec_repair_segments_sets: compare every share beyond the basis with the basis */
 
 typedef struct ec_ctx ec_ctx;
 typedef void *ec_stream; /* hipStream_t; NULL = the default stream */
@@ -183,6 +189,39 @@ int ec_rebuild_segments_sets(const ec_ctx *ctx, size_t nseg, const int *nshares,
  * when done.  Segments of more than 128 shares go through ec_decode_segments. */
 int ec_decode_segments_sets(const ec_ctx *ctx, size_t nseg, const int *nshares, const int *nums,
                             uint8_t *const *pieces, size_t nstripes, uint8_t *const *outs, ec_stream stream);
+/* Segment repair: regenerate lost pieces of nseg segments, each from its own
+ * share set, without decoding the segment.  Shares are given exactly as for
+ * ec_rebuild_segments_sets (flattened per segment, any order, device pointers
+ * of nstripes*ess bytes each).  Segment g's targets are entries [toff_g,
+ * toff_g + ntargets[g]) of `targets` (piece numbers, any order) and of `outs`
+ * (device pointers of nstripes*ess bytes each, piece layout: what
+ * ec_encode_segments writes for that piece); toff_g is the sum of the ntargets
+ * before it.  A target must not be among the segment's shares.  The basis is
+ * the k shares infectious Rebuild chooses, so a repair and a rebuild of one
+ * share set trust the same shares; piece t is their Lagrange interpolation at
+ * t's point, one GF(2^8) matrix per segment, solved on the host in closed form.
+ * Async on stream, no host synchronisation, no caller memory retained.  Every
+ * segment is validated before anything is queued: on an error nothing is
+ * written.  ntargets[g] == 0 skips segment g.  Up to k = 128.
+ *
+ * Without EC_FLAG_CHECK_SHARES, shares beyond the basis are ignored and
+ * dev_status may be NULL.  With it (at most 128 shares per segment), dev_status
+ * (nseg device int32) is required: every non-basis share is predicted from the
+ * basis in the same pass and compared (syndrome rows, nothing stored), and
+ * dev_status[g] becomes 0 when all agreed, 1 when any byte differed -- the
+ * segment's regenerated pieces must then not be used.  The status words are
+ * zeroed in stream order by the call.  Correction is not part of this call:
+ * for a flagged segment the caller runs ec_decode_segments on that segment's
+ * pieces (it corrects them in place, or reports EC_ERR_TOO_MANY_ERRORS) and
+ * repairs again.
+ *
+ * Segments whose share size is no multiple of 16, or with a pointer that is
+ * not 16-byte aligned, go one by one through the byte kernel (their matrix is
+ * uploaded as a cached plan on the context's own setup stream); same results. */
+int ec_repair_segments_sets(const ec_ctx *ctx, size_t nseg, const int *nshares, const int *nums,
+                            const uint8_t *const *pieces, const int *ntargets, const int *targets,
+                            uint8_t *const *outs, size_t nstripes, int flags, int32_t *dev_status,
+                            ec_stream stream);
 /* ec_rebuild_segments[_batched] with a share set the context has no
  * straight-line code for runs the share-set pass and has the code made in the
  * background (DESIGN.md §4 "Straight-line rebuild bodies"); later launches of

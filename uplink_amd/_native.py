@@ -30,6 +30,7 @@ EC_ERR_AUTH = -14
 
 EC_FLAG_PARITY_ONLY = 0x1
 EC_FLAG_HASH_PIECES = 0x2
+EC_FLAG_CHECK_SHARES = 0x4
 # ec_set_body: body of the runtime-matrix kernel (include/uplink_ec.h)
 EC_BODY_AUTO, EC_BODY_JUMP_TABLE, EC_BODY_STRAIGHT_LINE = 0, 1, 2
 # ec_bw_probe shapes
@@ -72,6 +73,10 @@ SIGNATURES = {
     "ec_decode_segments_sets": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp), ctypes.c_size_t,
                                                ctypes.POINTER(vp), vp]),
+    "ec_repair_segments_sets": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
+                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(vp), ctypes.c_size_t, ctypes.c_int, vp, vp]),
     "ec_prepare_rebuild": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "ec_encode_segments_host": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_int]),
     "ec_rebuild_segments_host": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),

@@ -485,6 +485,14 @@ int get_plan(ec_ctx *c, const std::vector<int> &ids, PlanPtr *out) {
     }, out);
 }
 
+int matrix_plan(ec_ctx *c, const std::vector<int> &key, const uint8_t *M, int rows, int nin, PlanPtr *out) {
+    return cached_plan(c, key, [&](std::vector<uint8_t> &m, int &r, std::vector<int> &) {
+        m.assign(M, M + (size_t)std::max(rows, 1) * nin);
+        r = rows;
+        return EC_OK;
+    }, out, nin);
+}
+
 // The rebuild of nseg segments from the chosen shares (order: their indices in
 // `pieces`, ids: their numbers) with a decode plan.
 int rebuild_with_plan(ec_ctx *c, MatPlan &plan, const std::vector<int> &order, const std::vector<int> &ids,
@@ -627,6 +635,7 @@ void ec_destroy(ec_ctx *c) {
         if (busy) (void)hipDeviceSynchronize();
         c->sets.slots.clear();
     }
+    c->repair.blocks.clear();  // (each waits for the event behind its last launch, then frees)
     for (int s = 0; s < HostPipe::kSlots; s++) {
         if (c->pipe.st[s]) (void)hipStreamSynchronize(c->pipe.st[s]), (void)hipStreamDestroy(c->pipe.st[s]);
         if (c->pipe.d_in[s]) (void)hipFree(c->pipe.d_in[s]);

@@ -24,6 +24,7 @@
 #include "gf256.hpp"
 #include "rs_correct.hpp"
 #include "rs_kernels.hpp"
+#include "rs_repair.hpp"
 #include "rs_sets.hpp"
 #include "rs_sl.hpp"
 
@@ -333,6 +334,65 @@ struct SetsRing {
     std::vector<std::unique_ptr<SetsSlot>> slots;
 };
 
+// Staging of one repair call (ec_repair_segments_sets, rs_repair.hpp): the
+// pinned memory the host writes its segments' records and coefficients into and
+// the device memory rs_repair_prep makes descriptors and leaf tables in.  An
+// event recorded behind the call's last launch tells when both are free again:
+// a block is taken under the pool's mutex, reused once its event has completed
+// (hipEventQuery, no wait), and another is made when none is free, so a call
+// waits for nothing queued earlier.  Blocks are sized in powers of two and kept
+// until ec_destroy (a free on the call path would synchronise the device).
+struct RepairBlock {
+    uint8_t *h = nullptr, *d = nullptr;
+    size_t h_cap = 0, d_cap = 0;
+    hipEvent_t ev = nullptr;
+    bool busy = false;    // a caller is filling or launching it
+    bool queued = false;  // ev is recorded behind launches that read the block
+    bool idle() const { return !busy && (!queued || hipEventQuery(ev) == hipSuccess); }
+    ~RepairBlock() {
+        if (queued && ev) (void)hipEventSynchronize(ev);
+        if (ev) (void)hipEventDestroy(ev);
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+    }
+};
+
+struct RepairPool {
+    // blocks in flight per context before a caller waits for the oldest (a
+    // caller that queues without end must not take pinned memory without end)
+    static constexpr size_t kMaxBlocks = 256;
+    std::mutex mu;
+    std::vector<std::unique_ptr<RepairBlock>> blocks;
+};
+
+// Lagrange interpolation through the points of k basis shares (piece numbers
+// ids[0..k)), in logarithms: the closed form of rs_sets.hip (solve_rows).
+// row(y, out): out[p] = L_p(y), the coefficient of basis share p in the share
+// at point y -- a unit vector when y is itself a basis point.
+struct LagrangeBasis {
+    int k = 0;
+    uint8_t x[kMaxOps];
+    int lw[kMaxOps];  // log W_p, W_p = prod over t != p of (x_p - x_t)
+    LagrangeBasis(const int *ids, int k_) : k(k_) {
+        for (int p = 0; p < k; p++) x[p] = gf_point(ids[p]);
+        for (int p = 0; p < k; p++) {
+            int l = 0;
+            for (int t = 0; t < k; t++)
+                if (t != p) l += kGf.log[x[p] ^ x[t]];
+            lw[p] = l % 255;
+        }
+    }
+    void row(uint8_t y, uint8_t *out) const {
+        int ln = 0, hit = -1;
+        for (int t = 0; t < k; t++) {
+            if (y == x[t]) hit = t;
+            else ln += kGf.log[y ^ x[t]];
+        }
+        for (int j = 0; j < k; j++)
+            out[j] = hit >= 0 ? (uint8_t)(hit == j) : kGf.exp[(((ln - kGf.log[y ^ x[j]] - lw[j]) % 255) + 255) % 255];
+    }
+};
+
 // Background maker of decode plans' straight-line code (DESIGN.md §4
 // "Straight-line rebuild bodies"): code generation and hipModuleLoadData take
 // ~0.4 ms per share set, so a batched rebuild never waits for them.  A launch
@@ -427,6 +487,7 @@ struct ec_ctx {
     // UPLINK_EC_SETS_ONE=0 at ec_create for the two launches (A/B)
     bool sets_one = true;
     SetsRing sets;
+    RepairPool repair;  // staging of ec_repair_segments_sets
     SlBuilder slb;
 };
 
@@ -458,6 +519,9 @@ int after_launch(uint32_t *chk, hipStream_t s);
 int choose_shares(const ec_ctx *c, int nshares, const int *nums, std::vector<int> &order_out,
                   std::vector<int> &ids_out);
 int get_plan(ec_ctx *c, const std::vector<int> &ids, PlanPtr *out);
+// cached plan of the rows x nin matrix M under `key` (repair's byte path: keys that start with -5)
+int matrix_plan(ec_ctx *c, const std::vector<int> &key, const uint8_t *M, int rows, int nin, PlanPtr *out);
+void fill_geometry(RsArgs &a, int ess, int64_t nstripes, int64_t nseg);
 void ensure_sl(ec_ctx *c, MatPlan &plan);
 int rebuild_with_plan(ec_ctx *c, MatPlan &plan, const std::vector<int> &order, const std::vector<int> &ids,
                       const uint8_t *const *pieces, int ess, int64_t nstripes, int64_t nseg, int64_t piece_seg_stride,

@@ -1,0 +1,204 @@
+"""Segment repair on the engine (include/uplink_ec.h ec_repair_segments_sets):
+the pieces a segment has lost, regenerated from any k of those it still has,
+without the decoded segment in between.
+
+What it stands in for: the repair and graceful-exit callers that sit on top of
+ecclient.Client (private/ecclient/client.go:36-44) fetch k pieces with Get,
+decode, and encode again for PutSingleResult / PutPiece (client.go:77-101).
+Here piece t is computed straight from the basis shares (Lagrange
+interpolation at t's point), a share set and a target set per segment, many
+segments in one stream-ordered pass.
+
+  repair_segments      the regenerated pieces of a batch of segments (optionally
+                       with every surplus share checked against the basis, flagged
+                       segments corrected through Decode and repaired again; and
+                       the BLAKE3 piece hashes PutPiece sends, piecestore/upload.go:270)
+  SegmentRepairer      which pieces to regenerate, by ecclient.put's threshold rule
+                       (client.go:113-116), and the repair of those
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Iterable, List, Sequence
+
+from . import _native as N
+from .eestream import NotEnoughShares, SegmentCodec, _raise
+
+
+def _ctx_of(scheme_or_ctx):
+    return scheme_or_ctx.ctx if hasattr(scheme_or_ctx, "ctx") else scheme_or_ctx
+
+
+def _flatten(segments):
+    """(nshares, nums, piece addresses, ntargets, targets) of a batch, as the C call takes them."""
+    nsh, nums, ptrs, ntg, tgts = [], [], [], [], []
+    for snums, pieces, targets in segments:
+        snums, pieces, targets = list(snums), list(pieces), list(targets)
+        if len(snums) != len(pieces):
+            raise ValueError("nums and pieces differ in length")
+        nsh.append(len(snums))
+        nums += [int(x) for x in snums]
+        ptrs += [SegmentCodec._addr(p) for p in pieces]
+        ntg.append(len(targets))
+        tgts += [int(t) for t in targets]
+    return nsh, nums, ptrs, ntg, tgts
+
+
+def _carr(ctype, values):
+    return (ctype * max(len(values), 1))(*values)
+
+
+def repair_call(ctx, segments, out_ptrs: Sequence[int], nstripes: int, flags: int = 0, status=None, stream=None) -> int:
+    """ec_repair_segments_sets on raw arguments; returns its code.  segments:
+    (nums, pieces, targets) each, pieces and out_ptrs device tensors or addresses."""
+    nsh, nums, ptrs, ntg, tgts = _flatten(segments)
+    out_ptrs = [SegmentCodec._addr(p) for p in out_ptrs]
+    if len(out_ptrs) != len(tgts):
+        raise ValueError("one output per target")
+    return N.load().ec_repair_segments_sets(
+        ctx, len(nsh), _carr(ctypes.c_int, nsh), _carr(ctypes.c_int, nums), _carr(ctypes.c_void_p, ptrs),
+        _carr(ctypes.c_int, ntg), _carr(ctypes.c_int, tgts), _carr(ctypes.c_void_p, out_ptrs), nstripes, flags,
+        SegmentCodec._addr(status) if status is not None else None, SegmentCodec._stream(stream))
+
+
+def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, stream=None):
+    """Regenerate the pieces `targets` of every segment of `segments`, each a
+    (nums, pieces, targets): the piece numbers it still has, their device
+    tensors (torch uint8, nstripes*ess bytes each, any order) and the piece
+    numbers wanted.  Returns, per segment, a [len(targets), nstripes*ess] uint8
+    device tensor whose row i is piece targets[i]; with hash_pieces, a pair of
+    that list and a list of [len(targets), 32] tensors of their BLAKE3 hashes.
+
+    check: every share beyond the k the repair is computed from is compared
+    with them in the same pass.  A segment where one disagrees is corrected as
+    Decode corrects it (its piece tensors are rewritten in place, as infectious
+    corrects share.Data) and repaired once more; infectious' TooManyErrors /
+    NotEnoughShares are raised as eestream words them.  With check the call
+    returns after the status has been read; without it, it is asynchronous on
+    `stream`."""
+    import torch
+
+    ctx = _ctx_of(scheme_or_ctx)
+    lib = N.load()
+    segments = [(list(a), list(b), list(c)) for a, b, c in segments]
+    ess = lib.ec_share_size(ctx)
+    k = lib.ec_required(ctx)
+    if ess <= 0 or k <= 0:
+        _raise(None, N.EC_ERR_INVALID_ARG)
+    plen = None
+    for _, pieces, _ in segments:
+        for p in pieces:
+            if plen is None:
+                plen = p.numel()
+            elif p.numel() != plen:
+                _raise(ctx, N.EC_ERR_SHARE_SIZE)
+    if plen is None:
+        return ([], []) if hash_pieces else []
+    if plen % ess:
+        _raise(ctx, N.EC_ERR_INVALID_ARG)
+    nstripes = plen // ess
+    dev = segments[0][1][0].device
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        outs = [torch.empty((len(t), plen), dtype=torch.uint8, device=dev) for _, _, t in segments]
+        rows = [o[i] for o in outs for i in range(o.shape[0])]
+        status = torch.empty(len(segments), dtype=torch.int32, device=dev) if check else None
+        flags = N.EC_FLAG_CHECK_SHARES if check else 0
+        _raise(ctx, repair_call(ctx, segments, rows, nstripes, flags, status, stream))
+
+        def read(t):  # (waits for the stream; a raw stream handle is not one torch's copy follows)
+            if stream is not None and ts is None:
+                torch.cuda.synchronize()
+            return t.cpu().tolist()
+
+        if check:
+            bad = [g for g, s in enumerate(read(status)) if s]
+            if bad:
+                scratch = torch.empty(nstripes * k * ess, dtype=torch.uint8, device=dev)
+                st = SegmentCodec._stream(stream)
+                for g in bad:
+                    nums, pieces, _ = segments[g]
+                    rc = lib.ec_decode_segments(ctx, len(nums), _carr(ctypes.c_int, nums),
+                                                _carr(ctypes.c_void_p, [p.data_ptr() for p in pieces]), nstripes,
+                                                scratch.data_ptr(), st)
+                    _raise(ctx, rc)
+                again = [segments[g] for g in bad]
+                st2 = torch.empty(len(bad), dtype=torch.int32, device=dev)
+                rows2 = [outs[g][i] for g in bad for i in range(outs[g].shape[0])]
+                _raise(ctx, repair_call(ctx, again, rows2, nstripes, flags, st2, stream))
+                if any(read(st2)):  # (corrected shares are codewords: not expected)
+                    _raise(ctx, N.EC_ERR_TOO_MANY_ERRORS)
+        if not hash_pieces:
+            return outs
+        hashes = [torch.empty((o.shape[0], 32), dtype=torch.uint8, device=dev) for o in outs]
+        for o, h in zip(outs, hashes):
+            if o.shape[0]:
+                rc = lib.ec_blake3_pieces(o.data_ptr(), o.shape[0], plen, plen, 0, 0, h.data_ptr(),
+                                          SegmentCodec._stream(stream))
+                _raise(ctx, rc)
+        return outs, hashes
+
+
+class _Null:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
+
+
+class SegmentRepairer:
+    """Which pieces of a segment to regenerate, and their repair.
+
+    The rule is ecclient.put's (client.go:113-116): a segment whose healthy
+    pieces number at most the repair threshold (and fewer than the optimal
+    threshold) is not acceptable as it stands.  Such a segment gets every piece
+    it lacks regenerated, up to the total count; one above the repair threshold
+    is left alone."""
+
+    def __init__(self, redundancy):
+        self.rs = redundancy
+
+    def needs_repair(self, healthy: Iterable[int]) -> bool:
+        h = len(self._healthy(healthy))
+        return h <= self.rs.repair_threshold() and h < self.rs.optimal_threshold()
+
+    def _healthy(self, healthy: Iterable[int]) -> List[int]:
+        nums = sorted(int(x) for x in healthy)
+        if len(set(nums)) != len(nums):
+            raise ValueError("a healthy piece number is repeated")
+        for x in nums:
+            if x < 0 or x >= self.rs.total_count():
+                raise ValueError(f"invalid share id: {x}")
+        return nums
+
+    def targets(self, healthy: Iterable[int]) -> List[int]:
+        """Piece numbers to regenerate given the healthy ones ([] above the
+        repair threshold); fewer healthy pieces than the required count cannot
+        be repaired (infectious.NotEnoughShares)."""
+        nums = self._healthy(healthy)
+        if len(nums) < self.rs.required_count():
+            raise NotEnoughShares("infectious: must specify at least the number of required shares")
+        if not self.needs_repair(nums):
+            return []
+        have = set(nums)
+        return [t for t in range(self.rs.total_count()) if t not in have]
+
+    def repair(self, segments: Sequence[Dict[int, object]], *, check: bool = False, hash_pieces: bool = False,
+               stream=None):
+        """segments: per segment a dict {piece number: device tensor} of its
+        healthy pieces.  Returns per segment a dict {piece number: regenerated
+        tensor} (empty where no repair is needed); with hash_pieces, also a dict
+        {piece number: 32-byte hash tensor} per segment."""
+        batch, tg = [], []
+        for seg in segments:
+            nums = list(seg.keys())
+            t = self.targets(nums)
+            tg.append(t)
+            batch.append((nums, [seg[x] for x in nums], t))
+        res = repair_segments(self.rs, batch, check=check, hash_pieces=hash_pieces, stream=stream)
+        outs, hashes = res if hash_pieces else (res, None)
+        pieces = [{t: o[i] for i, t in enumerate(ts)} for ts, o in zip(tg, outs)]
+        if not hash_pieces:
+            return pieces
+        return pieces, [{t: h[i] for i, t in enumerate(ts)} for ts, h in zip(tg, hashes)]
