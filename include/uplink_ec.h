@@ -27,6 +27,9 @@
  *                            StripeReader.ReadStripes  stripe.go:382-428
  *   ec_*_segments_sets       the same for many segments with a share set each:
  *                            one StripeReader per download, ecclient/client.go:273-308
+ *   ec_*_segments_sized      the same with a stripe count per segment: GetWithOptions sizes
+ *                            every download from its own size (client.go:302-303), so the
+ *                            downloads in flight at once differ in size
  *   ec_repair_segments_sets  segment repair: the lost pieces regenerated from any k, a
  *                            share set per segment -- what the repair and graceful-exit
  *                            callers of ecclient.Client do with Get + PutSingleResult /
@@ -189,6 +192,47 @@ int ec_rebuild_segments_sets(const ec_ctx *ctx, size_t nseg, const int *nshares,
  * when done.  Segments of more than 128 shares go through ec_decode_segments. */
 int ec_decode_segments_sets(const ec_ctx *ctx, size_t nseg, const int *nshares, const int *nums,
                             uint8_t *const *pieces, size_t nstripes, uint8_t *const *outs, ec_stream stream);
+/* ---- a share set and a size per segment ----
+ * The downloads in flight at once are of as many sizes as there are objects:
+ * the last segment of every object has its own size, small objects are one
+ * short segment each (GetWithOptions sizes every download from its own size,
+ * client.go:302-303).  These calls are the share-set calls above with a stripe
+ * count per segment, in one stream-ordered pass: each 2048-column tile finds
+ * its segment through a per-launch map, and the segment's descriptor carries
+ * its own geometry.  The decode rows are solved on the host in closed form (a
+ * few microseconds per segment) and staged in event-recycled blocks; a batch of
+ * thousands of segments goes in passes of bounded staging.  Every segment is
+ * validated before anything is queued: on an argument error nothing is
+ * written (too few shares, an invalid share number, a NULL pointer, a repeated
+ * chosen share: EC_ERR_SINGULAR, a segment whose nstripes[g]*ess/16 does not
+ * fit 32 bits: EC_ERR_UNSUPPORTED).  nstripes[g] == 0 skips segment g: nothing
+ * of it is read or written and outs[g] may be NULL.  Segments whose share size
+ * is no multiple of 16, or with a pointer that is not 16-byte aligned, go one
+ * by one through ec_rebuild_segments / ec_decode_segments' path with their own
+ * stripe count; same results.  Up to k = 128.  Not under stream capture
+ * (EC_ERR_UNSUPPORTED).
+ *
+ * ec_rebuild_segments_sets with a stripe count per segment: segment g has
+ * nstripes[g] stripes, its shares are nstripes[g]*ess bytes each, its output
+ * nstripes[g]*k*ess bytes.  Async on stream. */
+int ec_rebuild_segments_sized(const ec_ctx *ctx, size_t nseg, const int *nshares, const int *nums,
+                              const uint8_t *const *pieces, const size_t *nstripes, uint8_t *const *outs,
+                              ec_stream stream);
+/* ec_decode_segments_sets likewise (up to 128 shares per segment in the pass;
+ * segments with more go through ec_decode_segments on their own).  seg_rc
+ * (host, nseg ints, may be NULL): segment g's own outcome (EC_OK,
+ * EC_ERR_TOO_MANY_ERRORS, ...).  A failing segment does not stop the others:
+ * every flagged segment is corrected in its pieces and rebuilt as
+ * ec_decode_segments does, and the outputs of segments that succeeded are
+ * complete.  EC_ERR_NOT_ENOUGH_SHARES is only ever the call's argument error
+ * (a segment with fewer than k shares, nothing written): a segment in which an
+ * error is detected but whose surplus is too small to correct any (fewer than
+ * k + 2 shares, where infectious' Decode says NotEnoughShares) has
+ * EC_ERR_TOO_MANY_ERRORS as its outcome.  Returns the first non-OK outcome in
+ * segment order; returns when done. */
+int ec_decode_segments_sized(const ec_ctx *ctx, size_t nseg, const int *nshares, const int *nums,
+                             uint8_t *const *pieces, const size_t *nstripes, uint8_t *const *outs, int *seg_rc,
+                             ec_stream stream);
 /* Segment repair: regenerate lost pieces of nseg segments, each from its own
  * share set, without decoding the segment.  Shares are given exactly as for
  * ec_rebuild_segments_sets (flattened per segment, any order, device pointers

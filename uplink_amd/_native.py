@@ -73,6 +73,13 @@ SIGNATURES = {
     "ec_decode_segments_sets": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp), ctypes.c_size_t,
                                                ctypes.POINTER(vp), vp]),
+    "ec_rebuild_segments_sized": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
+                                                 ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(vp), vp]),
+    "ec_decode_segments_sized": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
+                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
+                                                ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(vp),
+                                                ctypes.POINTER(ctypes.c_int), vp]),
     "ec_repair_segments_sets": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),

@@ -488,6 +488,11 @@ struct ec_ctx {
     bool sets_one = true;
     SetsRing sets;
     RepairPool repair;  // staging of ec_repair_segments_sets
+    RepairPool sized;   // staging of ec_*_segments_sized (ec_sized.cpp): the same mechanism, a pool of its own
+    // the sized calls launch per wave-count class; UPLINK_EC_SIZED_MERGE=1 at ec_create puts every
+    // segment of a pass on the widest class's workgroups instead (one launch, one tail, as
+    // sets_merge does for the share-set calls): the A/B of DESIGN.md §4h
+    bool sized_merge = false;
     SlBuilder slb;
 };
 

@@ -1,0 +1,354 @@
+// C-ABI, share-set calls with a size per segment (include/uplink_ec.h
+// ec_rebuild_segments_sized, ec_decode_segments_sized): a batch of downloads of
+// as many sizes as objects, each rebuilt or decoded from its own share set, in
+// one stream-ordered pass (rs_sized.hpp).  The host chooses the basis as
+// Rebuild does, solves each segment's rows in closed form (LagrangeBasis) and
+// stages them with the geometry (sized_geom.hpp) in event-recycled blocks, as
+// segment repair does (ec_repair.cpp); nothing on the Rebuild path waits for
+// the stream.
+#include "ec_internal.hpp"
+#include "rs_sized.hpp"
+#include "sized_geom.hpp"
+
+namespace uplink_ec {
+namespace capi {
+namespace {
+
+// One segment of a sized call as the host prepares it: the inputs in the
+// kernel's order (infectious' k chosen shares by position, then -- Decode --
+// the other shares by number) and the rows (missing data positions, then one
+// syndrome row per non-basis input).
+struct SizedSeg {
+    std::vector<const uint8_t *> in;
+    std::vector<int> num;
+    std::vector<int> missing;
+    uint8_t *out = nullptr;
+    size_t g = 0;  // segment of the call
+    int64_t nstripes = 0, chunks = 0, tiles = 0;
+    int rows = 0, nw = 2;
+    bool bits = true;  // the bit-sliced pass takes it
+    bool own = false;  // Decode of more shares than a launch takes: ec_decode_segments on its own
+};
+
+// Fill `sg` from (nshares, nums, pieces).  Errors as Rebuild / Decode report
+// them (an invalid share id, a repeated share chosen twice: singular).
+int prepare_segment(const ec_ctx *c, int nshares, const int *nums, const uint8_t *const *pieces, bool decode,
+                    SizedSeg &sg) {
+    const int k = c->k;
+    if (decode)
+        for (int i = 0; i < nshares; i++)
+            if (nums[i] < 0 || nums[i] >= c->n) return EC_ERR_INVALID_SHARE;
+    std::vector<int> order, ids;
+    if (int rc = choose_shares(c, nshares, nums, order, ids)) return rc;
+    bool seen[256] = {};
+    std::vector<char> chosen(nshares, 0);
+    for (int i = 0; i < k; i++) {
+        if (seen[ids[i]]) return EC_ERR_SINGULAR;
+        seen[ids[i]] = true;
+        chosen[order[i]] = 1;
+        sg.in.push_back(pieces[order[i]]);
+        sg.num.push_back(ids[i]);
+        if (ids[i] >= k) sg.missing.push_back(i);
+    }
+    sg.own = decode && nshares > kMaxOps;
+    if (decode && !sg.own) {  // the other shares, by number (as the share-set decode orders them)
+        std::vector<int> rest;
+        for (int i = 0; i < nshares; i++)
+            if (!chosen[i]) rest.push_back(i);
+        std::stable_sort(rest.begin(), rest.end(), [&](int x, int y) { return nums[x] < nums[y]; });
+        for (int i : rest) {
+            sg.in.push_back(pieces[i]);
+            sg.num.push_back(nums[i]);
+        }
+    }
+    sg.rows = (int)sg.missing.size() + (int)sg.in.size() - k;
+    sg.nw = sets_waves(sg.rows);
+    return EC_OK;
+}
+
+// Row r of the segment's matrix (nin columns): missing data position r from the
+// basis, then one syndrome row per non-basis input (its prediction from the
+// basis, and 1 on the input itself: the two cancel when the share agrees).
+void solve_rows(const SizedSeg &sg, int k, std::vector<uint8_t> &M) {
+    const int nin = (int)sg.in.size(), nst = (int)sg.missing.size();
+    const LagrangeBasis L(sg.num.data(), k);
+    M.assign((size_t)std::max(sg.rows, 1) * nin, 0);
+    for (int r = 0; r < sg.rows; r++) {
+        L.row(gf_point(r < nst ? sg.missing[r] : sg.num[k + r - nst]), &M[(size_t)r * nin]);
+        if (r >= nst) M[(size_t)r * nin + k + r - nst] = 1;
+    }
+}
+
+size_t pow2_at_least(size_t n, size_t lo) {
+    size_t c = lo;
+    while (c < n) c *= 2;
+    return c;
+}
+
+// A block of the context's sized pool with room for h_need pinned and d_need
+// device bytes whose previous pass has finished on the GPU, or a new one (sized
+// in powers of two).  nullptr: no memory.  (RepairBlock's mechanism, ec_repair.cpp.)
+RepairBlock *sized_acquire(ec_ctx *c, size_t h_need, size_t d_need) {
+    RepairPool &P = c->sized;
+    RepairBlock *b = nullptr, *oldest = nullptr;
+    {
+        std::lock_guard<std::mutex> g(P.mu);
+        for (auto &x : P.blocks) {
+            if (x->busy) continue;
+            if (x->h_cap < h_need || x->d_cap < d_need) continue;
+            if (!oldest) oldest = x.get();
+            if (x->idle()) {
+                b = x.get();
+                break;
+            }
+        }
+        if (!b && P.blocks.size() >= RepairPool::kMaxBlocks) b = oldest;  // waited for below
+        if (!b) {
+            auto x = std::make_unique<RepairBlock>();
+            x->h_cap = pow2_at_least(h_need, 64u << 10);
+            x->d_cap = pow2_at_least(d_need, 512u << 10);
+            if (hipHostMalloc((void **)&x->h, x->h_cap, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+                hipMalloc((void **)&x->d, x->d_cap) != hipSuccess ||
+                hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess)
+                return nullptr;  // (its destructor frees what it got)
+            P.blocks.push_back(std::move(x));
+            b = P.blocks.back().get();
+        }
+        b->busy = true;
+    }
+    if (b->queued && hipEventSynchronize(b->ev) != hipSuccess) {
+        std::lock_guard<std::mutex> g(P.mu);
+        b->busy = false;
+        return nullptr;
+    }
+    b->queued = false;
+    return b;
+}
+
+// Hand the block back; `launched`: something that reads it was queued on s.
+void sized_release(ec_ctx *c, RepairBlock *b, bool launched, hipStream_t s) {
+    // (an event that cannot be recorded leaves the block to a wait for the stream)
+    if (launched && hipEventRecord(b->ev, s) != hipSuccess) (void)hipStreamSynchronize(s);
+    std::lock_guard<std::mutex> g(c->sized.mu);
+    b->queued = launched;
+    b->busy = false;
+}
+
+size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// One pass over segs[0..n): rs_sized_prep, then the tile kernel per wave-count
+// class (in parts where a class has more tiles than a launch takes), all on
+// stream s.  With `bad` (Decode), waits and returns per segment the count of
+// syndrome failures.
+int sized_pass(ec_ctx *c, SizedSeg *const *segs, size_t n, hipStream_t s, std::vector<uint32_t> *bad) {
+    const int k = c->k, ess = c->ess;
+    std::vector<int> nw(n);
+    std::vector<int64_t> tiles(n);
+    int widest = 2;
+    for (size_t i = 0; i < n; i++) widest = std::max(widest, segs[i]->nw);
+    for (size_t i = 0; i < n; i++) {
+        if (c->sized_merge) segs[i]->nw = widest;  // (the A/B knob: one class, one launch)
+        nw[i] = segs[i]->nw;
+        tiles[i] = segs[i]->tiles;
+    }
+    const sized::Layout L = sized::layout(nw.data(), tiles.data(), n, sets_max_tiles);
+    std::vector<size_t> eoff(n + 1, 0);
+    for (size_t q = 0; q < n; q++) {
+        const SizedSeg &sg = *segs[L.idx[q]];
+        eoff[q + 1] = eoff[q] + sized_tgt_entries((int)sg.in.size(), sg.rows, sg.nw);
+    }
+    const size_t h_stage = up(n * sizeof(SizedStage), 16), h_coef_len = eoff[n];
+    const size_t d_desc = up(n * sizeof(SizedDesc), 256), d_tgt_len = eoff[n] * 8;
+    const size_t d_map_len = up((size_t)L.map_entries * 4, 256);
+    RepairBlock *b = sized_acquire(c, h_stage + h_coef_len + n * 4, d_desc + d_tgt_len + d_map_len + n * 4);
+    if (!b) return EC_ERR_DEVICE;
+    SizedStage *stage = (SizedStage *)b->h;
+    uint8_t *h_coef = b->h + h_stage;
+    uint32_t *h_cnt = (uint32_t *)(b->h + h_stage + h_coef_len);
+    SizedDesc *d_descs = (SizedDesc *)b->d;
+    uint64_t *d_tgt = (uint64_t *)(b->d + d_desc);
+    uint32_t *d_map = (uint32_t *)(b->d + d_desc + d_tgt_len);
+    uint32_t *d_cnt = (uint32_t *)(b->d + d_desc + d_tgt_len + d_map_len);
+    std::vector<uint8_t> M;
+    for (size_t q = 0; q < n; q++) {
+        const SizedSeg &sg = *segs[L.idx[q]];
+        const int nin = (int)sg.in.size(), nst = (int)sg.missing.size(), w = sg.nw;
+        SizedStage &st = stage[q];
+        memset(&st, 0, sizeof(st));
+        for (int j = 0; j < nin; j++) {
+            st.d.in[j] = sg.in[j];
+            st.d.copy_off[j] = j < k && sg.num[j] < k ? sg.num[j] * ess : -1;
+        }
+        for (int r = 0; r < nst; r++) st.d.out_off[r] = sg.missing[r] * ess;
+        st.d.out = sg.out;
+        st.d.tgt = d_tgt + eoff[q];
+        st.d.zero_check = bad ? d_cnt + q : nullptr;
+        st.d.nin = nin;
+        st.d.nout = sg.rows;
+        st.d.nstore = nst;
+        st.d.chunks = sg.chunks;
+        st.d.piece_len = sg.nstripes * ess;
+        st.d.spad = sg.nstripes * ess * k;
+        st.d.tile0 = L.tile0[q];
+        st.coef = h_coef + eoff[q];
+        st.entries = (int64_t)(eoff[q + 1] - eoff[q]);
+        st.map = d_map + L.map_off[q] + L.tile0[q];
+        st.ntiles = sg.tiles;
+        // the coefficients in the leaf table's order: [pass][input][group][8], a group's rows right-aligned
+        solve_rows(sg, k, M);
+        uint8_t *cf = h_coef + eoff[q];
+        memset(cf, 0, (size_t)st.entries);
+        const int npass = sized_npass(sg.rows, w);
+        for (int pass = 0; pass < npass; pass++)
+            for (int g = 0; g < w; g++) {
+                int rb, cn;
+                sized_rows_of(pass, npass, sg.rows, w, g, rb, cn);
+                for (int j = 0; j < nin; j++) {
+                    uint8_t *e = cf + (((size_t)pass * nin + j) * w + g) * 8 + (8 - cn);
+                    for (int o = 0; o < cn; o++) e[o] = M[(size_t)(rb + o) * nin + j];
+                }
+            }
+    }
+    hipError_t e = launch_sized_prep(stage, d_descs, (int)n, c->jt_base, s);
+    if (e != hipSuccess) {  // nothing was queued
+        sized_release(c, b, false, s);
+        return hip_fail(e);
+    }
+    for (const sized::Launch &ln : L.launches) {
+        SizedArgs a{};
+        a.desc = d_descs;
+        a.map = d_map + ln.map_off;
+        a.tile_base = ln.tile_base;
+        a.total_tiles = ln.tiles;
+        a.ess = ess;
+        a.cps = ess / 16;
+        a.k = k;
+        a.chk_flag = c->d_chk;
+        e = launch_matmul_sized(a, ln.nw, s);
+        if (e != hipSuccess) break;
+    }
+    if (e == hipSuccess && bad) {
+        // (the block stays this caller's until the counts are read: Decode returns when done)
+        e = hipMemcpyAsync(h_cnt, d_cnt, n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        bad->assign(n, 0);
+        for (size_t q = 0; q < n && e == hipSuccess; q++) (*bad)[L.idx[q]] = h_cnt[q];
+    }
+    sized_release(c, b, true, s);
+    if (e != hipSuccess) return hip_fail(e);
+    c->last_body = EC_BODY_JUMP_TABLE;
+    return after_launch(c->d_chk, s);
+}
+
+int sized_call(ec_ctx *c, size_t nseg, const int *nshares, const int *nums, const uint8_t *const *pieces,
+               const size_t *nstripes, uint8_t *const *outs, int *seg_rc, hipStream_t s, bool decode, bool *queued) {
+    const int k = c->k, ess = c->ess;
+    *queued = false;
+    if (k > kMaxOps) return EC_ERR_UNSUPPORTED;
+    // every segment is validated before anything is queued
+    std::vector<size_t> off(nseg + 1, 0);
+    for (size_t g = 0; g < nseg; g++) off[g + 1] = off[g] + (size_t)std::max(nshares[g], 0);
+    std::vector<SizedSeg> segs;
+    for (size_t g = 0; g < nseg; g++) {
+        if (nstripes[g] == 0) continue;
+        const int ns = nshares[g];
+        if (ns < k) return EC_ERR_NOT_ENOUGH_SHARES;
+        if (!outs[g]) return EC_ERR_INVALID_ARG;
+        const uint8_t *const *sp = pieces + off[g];
+        for (int i = 0; i < ns; i++)
+            if (!sp[i]) return EC_ERR_INVALID_ARG;
+        const int64_t chunks = sized::chunks_of(nstripes[g], ess);
+        if (chunks < 0) return EC_ERR_UNSUPPORTED;
+        segs.emplace_back();
+        SizedSeg &sg = segs.back();
+        if (int rc = prepare_segment(c, ns, nums + off[g], sp, decode, sg)) return rc;
+        sg.g = g;
+        sg.out = outs[g];
+        sg.nstripes = (int64_t)nstripes[g];
+        sg.chunks = chunks;
+        sg.tiles = sized::tiles_of(chunks);
+        sg.bits = !sg.own && ess % 16 == 0 && aligned16(outs[g]);
+        for (int i = 0; i < ns; i++) sg.bits = sg.bits && aligned16(sp[i]);
+    }
+    // staging blocks are recycled by events behind launches that run: not under stream capture
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    *queued = true;
+    std::vector<int> rcs(nseg, EC_OK);
+    // A segment's own outcome.  Too few shares is an argument error of the call, found above
+    // before anything is queued (every segment here has at least k).  infectious words one
+    // more case that way: an error detected where the surplus is too small to correct any
+    // (fewer than k + 2 shares, Berlekamp-Welch's e = 0).  As a segment's outcome that is more
+    // errors than its shares correct: EC_ERR_TOO_MANY_ERRORS.
+    auto decode_own = [&](size_t g) {
+        const int rc = ec_decode_segments(c, nshares[g], nums + off[g], (uint8_t *const *)pieces + off[g], nstripes[g],
+                                          outs[g], (ec_stream)s);
+        return rc == EC_ERR_NOT_ENOUGH_SHARES ? EC_ERR_TOO_MANY_ERRORS : rc;
+    };
+    // byte kernel / more inputs than a launch takes: such a segment on its own, with its own stripe count
+    std::vector<SizedSeg *> list;
+    for (SizedSeg &sg : segs) {
+        if (sg.bits) {
+            list.push_back(&sg);
+            continue;
+        }
+        const size_t g = sg.g;
+        if (decode) {
+            rcs[g] = decode_own(g);
+        } else if (int rc = rebuild_device(c, nshares[g], nums + off[g], pieces + off[g], ess, sg.nstripes, 1, 0, 0,
+                                           outs[g], s)) {
+            return rc;
+        }
+    }
+    std::vector<int64_t> tiles(list.size());
+    for (size_t i = 0; i < list.size(); i++) tiles[i] = list[i]->tiles;
+    for (const sized::Pass &p : sized::split_passes(tiles.data(), list.size(), sized::kPassSegs, sized::kPassTiles)) {
+        std::vector<uint32_t> bad;
+        if (int rc = sized_pass(c, list.data() + p.i0, p.i1 - p.i0, s, decode ? &bad : nullptr)) return rc;
+        // Decode: a segment whose syndromes are not all zero is corrected (in the caller's
+        // pieces, as infectious corrects share.Data) and rebuilt on its own; its outcome is
+        // its own, and the others go on
+        for (size_t i = p.i0; i < p.i1 && decode; i++)
+            if (bad[i - p.i0]) rcs[list[i]->g] = decode_own(list[i]->g);
+    }
+    int first = EC_OK;
+    for (size_t g = 0; g < nseg; g++) {
+        if (seg_rc) seg_rc[g] = rcs[g];
+        if (first == EC_OK) first = rcs[g];
+    }
+    return first;
+}
+
+}  // namespace
+}  // namespace capi
+}  // namespace uplink_ec
+
+extern "C" {
+
+int ec_rebuild_segments_sized(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums,
+                              const uint8_t *const *pieces, const size_t *nstripes, uint8_t *const *outs,
+                              ec_stream stream) {
+    ec_ctx *c = const_cast<ec_ctx *>(cc);
+    if (!c || (nseg && (!nshares || !nums || !pieces || !nstripes || !outs))) return EC_ERR_INVALID_ARG;
+    if (nseg == 0) return EC_OK;
+    DeviceGuard dg(c->device);
+    bool queued;
+    return sized_call(c, nseg, nshares, nums, pieces, nstripes, outs, nullptr, (hipStream_t)stream, false, &queued);
+}
+
+int ec_decode_segments_sized(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums,
+                             uint8_t *const *pieces, const size_t *nstripes, uint8_t *const *outs, int *seg_rc,
+                             ec_stream stream) {
+    ec_ctx *c = const_cast<ec_ctx *>(cc);
+    if (!c || (nseg && (!nshares || !nums || !pieces || !nstripes || !outs))) return EC_ERR_INVALID_ARG;
+    if (nseg == 0) return EC_OK;
+    DeviceGuard dg(c->device);
+    bool queued;
+    int rc = sized_call(c, nseg, nshares, nums, (const uint8_t *const *)pieces, nstripes, outs, seg_rc,
+                        (hipStream_t)stream, true, &queued);
+    // (nothing to wait for after an argument error, and no wait on a capturing stream)
+    if (queued && hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == EC_OK) rc = EC_ERR_DEVICE;
+    return rc;
+}
+
+}  // extern "C"

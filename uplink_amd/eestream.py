@@ -445,6 +445,9 @@ class SegmentCodec:
     decode_segments_sets(sets, nstripes, outs, stream=None)
         sets   one (nums, piece_ptrs) per segment: each segment with its own share set
         outs   one [nstripes][k][ess] output per segment
+    rebuild_segments_sized(sets, nstripes, outs, stream=None)
+    decode_segments_sized(sets, nstripes, outs, stream=None, collect=False)
+        the same with nstripes a sequence: a stripe count per segment
     """
 
     def __init__(self, scheme: RSScheme):
@@ -535,3 +538,39 @@ class SegmentCodec:
         rc = self._lib.ec_decode_segments_sets(self.scheme.ctx, nseg, nsh, nums, ptrs, nstripes, optr,
                                                self._stream(stream))
         _raise(self.scheme.ctx, rc)
+
+    def _sized_args(self, sets, nstripes, outs):
+        nstripes = [int(x) for x in nstripes]
+        if len(nstripes) != len(sets):
+            raise ValueError("one stripe count per segment")
+        if any(x < 0 for x in nstripes):
+            raise ValueError("a stripe count is negative")
+        # (a skipped segment's output may be None)
+        outs = [0 if o is None else o for o in outs]
+        return self._sets_args(sets, outs), (ctypes.c_size_t * max(len(nstripes), 1))(*nstripes)
+
+    def rebuild_segments_sized(self, sets, nstripes, outs, stream=None):
+        """rebuild_segments_sets with a stripe count per segment
+        (ec_rebuild_segments_sized): the downloads in flight at once differ in
+        size (client.go:302-303), and one stream-ordered pass serves them all.
+        nstripes[g] == 0 skips segment g.  Asynchronous on `stream`."""
+        (nseg, nsh, nums, ptrs, optr), nst = self._sized_args(sets, nstripes, outs)
+        rc = self._lib.ec_rebuild_segments_sized(self.scheme.ctx, nseg, nsh, nums, ptrs, nst, optr,
+                                                 self._stream(stream))
+        _raise(self.scheme.ctx, rc)
+
+    def decode_segments_sized(self, sets, nstripes, outs, stream=None, collect: bool = False):
+        """decode_segments_sets with a stripe count per segment
+        (ec_decode_segments_sized).  A failing segment does not stop the others;
+        returns the per-segment codes (EC_OK, EC_ERR_TOO_MANY_ERRORS, ...) when
+        done.  Unless `collect`, the first non-OK outcome raises as
+        decode_segments_sets raises it."""
+        (nseg, nsh, nums, ptrs, optr), nst = self._sized_args(sets, nstripes, outs)
+        seg_rc = (ctypes.c_int * max(nseg, 1))()
+        rc = self._lib.ec_decode_segments_sized(self.scheme.ctx, nseg, nsh, nums, ptrs, nst, optr, seg_rc,
+                                                self._stream(stream))
+        codes = [int(seg_rc[g]) for g in range(nseg)]
+        # (an argument error is the call's, not a segment's: every code is still EC_OK)
+        if rc != N.EC_OK and (not collect or all(x == N.EC_OK for x in codes)):
+            _raise(self.scheme.ctx, rc)
+        return codes
