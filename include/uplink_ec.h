@@ -131,6 +131,39 @@ int ec_decode(const ec_ctx *ctx, int nshares, int *nums, uint8_t **shares, size_
  *       EncodeSingle(stripe, num=i) over its stripes. */
 int ec_encode_segments(const ec_ctx *ctx, const uint8_t *segs, size_t nseg, size_t nstripes, uint8_t *pieces,
                        int flags, ec_stream stream);
+/* ---- a size per segment (the upload path as uplink runs it) ----
+ * The uploads in flight at once are of as many sizes as there are objects: the
+ * last segment of every object has its own size, a small object is one short
+ * segment (single.go:233-238 pads and encodes each segment from its own length;
+ * segmentupload/encode.go:39-75 reads the n pieces of that one segment).  This
+ * is ec_encode_segments with a stripe count per segment, in one stream-ordered
+ * pass: segs[g] is a device pointer to segment g, nstripes[g]*k*ess bytes,
+ * stripe-major as above; pieces[g] a device pointer to its [n][nstripes[g]*ess]
+ * (or [n-k][...] with EC_FLAG_PARITY_ONLY), the layout ec_encode_segments
+ * writes for one segment.
+ * data_len == NULL: the segments are already padded and are only read.
+ * data_len != NULL: segment g holds data_len[g] bytes, and the call writes
+ * PadReader's padding behind them, in stream order before the encode: the
+ * bytes ec_pad_segments(segs[g], 1, 0, data_len[g], k*ess, stream) writes.  It
+ * requires nstripes[g]*k*ess == data_len[g] + p, p = 4 + (k*ess -
+ * (data_len[g] + 4) % (k*ess)) % (k*ess); otherwise EC_ERR_INVALID_ARG.
+ * Every segment is validated before anything is queued: on an argument error
+ * nothing is written (a NULL segs[g] or pieces[g] with nstripes[g] > 0:
+ * EC_ERR_INVALID_ARG; a segment whose nstripes[g]*ess/16 does not fit 32 bits:
+ * EC_ERR_UNSUPPORTED).  nstripes[g] == 0 skips segment g: nothing of it is
+ * looked at, and its pointers may be NULL.  Codes with a library-built
+ * compile-time encoder (ec_encode_kernel_name "special", not "special-jit")
+ * go through that encoder's sized form, each 1-KiB column block finding its
+ * segment through a per-pass map; a segment of another code, with a share size
+ * that is no multiple of 16 or with a pointer that is not 16-byte aligned goes
+ * on its own through ec_pad_segments and ec_encode_segments' path with its own
+ * stripe count; same results.  The call never starts a run-time compile.  A
+ * batch of thousands of segments goes in passes of bounded staging.  Async on
+ * stream, no host synchronisation once the staging pool is warm.  Not under
+ * stream capture (EC_ERR_UNSUPPORTED).  Up to k = 128. */
+int ec_encode_segments_sized(const ec_ctx *ctx, size_t nseg, uint8_t *const *segs, const size_t *nstripes,
+                             const size_t *data_len /* may be NULL */, uint8_t *const *pieces, int flags,
+                             ec_stream stream);
 /* Rebuild whole segments from nshares >= k pieces (each nstripes*ess bytes,
  * device pointers in `pieces`, piece numbers in `nums`, any order).  The
  * share choice follows infectious Rebuild; out = nstripes*k*ess bytes,

@@ -57,6 +57,9 @@ SIGNATURES = {
     "ec_decode": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
                                  ctypes.c_size_t, vp]),
     "ec_encode_segments": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_int, vp]),
+    "ec_encode_segments_sized": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp),
+                                                ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                                ctypes.POINTER(vp), ctypes.c_int, vp]),
     "ec_rebuild_segments": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
                                            ctypes.c_size_t, vp, vp]),
     "ec_decode_segments": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),

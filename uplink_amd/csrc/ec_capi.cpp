@@ -638,6 +638,7 @@ void ec_destroy(ec_ctx *c) {
     }
     c->repair.blocks.clear();  // (each waits for the event behind its last launch, then frees)
     c->sized.blocks.clear();   // (the same)
+    c->enc_sized.blocks.clear();
     for (int s = 0; s < HostPipe::kSlots; s++) {
         if (c->pipe.st[s]) (void)hipStreamSynchronize(c->pipe.st[s]), (void)hipStreamDestroy(c->pipe.st[s]);
         if (c->pipe.d_in[s]) (void)hipFree(c->pipe.d_in[s]);
@@ -731,7 +732,7 @@ int ec_prepare_encoder(const ec_ctx *c, int wait) {
 namespace uplink_ec {
 namespace capi {
 int encode_range(ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstripes, size_t s0, size_t s1,
-                        uint8_t *pieces, int flags, hipStream_t s, bool shape_probe) {
+                        uint8_t *pieces, int flags, hipStream_t s, bool shape_probe, bool no_jit) {
     if (!c || !segs || !pieces) return EC_ERR_INVALID_ARG;
     if (nseg == 0 || s1 <= s0) return EC_OK;
     const int k = c->k, n = c->n, ess = c->ess;
@@ -769,7 +770,7 @@ int encode_range(ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstripes, s
         // large enough to pay for it: never by per-stripe or few-stripe work)
         const EncoderKernel *ek = shape_probe ? shape_probe_encoder(k, n)
                                   : sl        ? nullptr
-                                              : find_encoder(c->k, c->n, false, a.total_tiles >= kJitMinTiles);
+                                              : find_encoder(c->k, c->n, false, !no_jit && a.total_tiles >= kJitMinTiles);
         if (ek) {
             a.coef = nullptr;
             set_extents(a, (int64_t)nseg, c->d_chk);

@@ -493,6 +493,7 @@ struct ec_ctx {
     // segment of a pass on the widest class's workgroups instead (one launch, one tail, as
     // sets_merge does for the share-set calls): the A/B of DESIGN.md §4h
     bool sized_merge = false;
+    RepairPool enc_sized;  // staging of ec_encode_segments_sized (ec_encode_sized.cpp): a pool of its own
     SlBuilder slb;
 };
 
@@ -533,9 +534,13 @@ int rebuild_with_plan(ec_ctx *c, MatPlan &plan, const std::vector<int> &order, c
                       int64_t out_seg_stride, uint8_t *out, hipStream_t s);
 int rebuild_device(ec_ctx *c, int nshares, const int *nums, const uint8_t *const *pieces, int ess, int64_t nstripes,
                    int64_t nseg, int64_t piece_seg_stride, int64_t out_seg_stride, uint8_t *out, hipStream_t s);
-// shape_probe: run the encoder's no-arithmetic form instead (ec_encode_shape_probe)
+// the compile-time encoder's work counters (QueueRing): a zeroed pair for one launch on s, or nullptr
+uint32_t *queue_take(ec_ctx *c, hipStream_t s, int *slot, uint32_t *seq, uint32_t **done);
+void queue_done(ec_ctx *c, hipStream_t s, int slot, uint32_t seq, bool launched);
+// shape_probe: run the encoder's no-arithmetic form instead (ec_encode_shape_probe);
+// no_jit: never start a run-time compile of this code's encoder (ec_encode_segments_sized)
 int encode_range(ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstripes, size_t s0, size_t s1,
-                 uint8_t *pieces, int flags, hipStream_t s, bool shape_probe = false);
+                 uint8_t *pieces, int flags, hipStream_t s, bool shape_probe = false, bool no_jit = false);
 size_t align_up(size_t x, size_t a);
 B3View data_view(const ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstripes);
 B3View parity_view(const ec_ctx *c, const uint8_t *parity, size_t nseg, size_t nstripes);

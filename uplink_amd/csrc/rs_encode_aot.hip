@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rs_encoder.hpp"
+#include "rs_encoder_sized.hpp"
 #include "rs_kernels.hpp"
 
 #define UPLINK_AOT_NAME2(K, N) aot_encoder_##K##_##N
@@ -23,6 +24,11 @@ EncoderKernel UPLINK_AOT_NAME(UPLINK_AOT_K, UPLINK_AOT_N)() {
               enc::wgs_per_cu(K, FNC + FNL), "rs_encode_special (library)"};
     e.parity = {reinterpret_cast<const void *>(&enc::rs_encode_special<K, N, PNC, PNL, false>), nullptr, (PNC + PNL) * 64,
                 enc::wgs_per_cu(K, PNC + PNL), "rs_encode_special (library, parity only)"};
+    // the same bodies with a geometry per segment (ec_encode_segments_sized)
+    e.sized_full = {reinterpret_cast<const void *>(&enc::rs_encode_sized<K, N, FNC, FNL, true>), nullptr, (FNC + FNL) * 64,
+                    enc::wgs_per_cu(K, FNC + FNL), "rs_encode_sized (library)"};
+    e.sized_parity = {reinterpret_cast<const void *>(&enc::rs_encode_sized<K, N, PNC, PNL, false>), nullptr,
+                      (PNC + PNL) * 64, enc::wgs_per_cu(K, PNC + PNL), "rs_encode_sized (library, parity only)"};
     return e;
 }
 

@@ -26,6 +26,8 @@ struct EncoderKernel {
     int k = 0, n = 0;
     bool jit = false;
     Variant full, parity;
+    // the same two with a geometry per segment (rs_encoder_sized.hpp); library-built encoders only
+    Variant sized_full, sized_parity;
 };
 
 // The encoder for (k, n) on the current device, or nullptr when (k, n) is

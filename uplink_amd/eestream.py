@@ -438,6 +438,8 @@ class SegmentCodec:
     encode_segments(segs, nseg, nstripes, pieces, parity_only=False, stream=None)
         segs   [nseg][nstripes][k][ess]  (padded, stripe-major)
         pieces [nseg][n][nstripes*ess]   ([nseg][n-k][...] when parity_only)
+    encode_segments_sized(segs, nstripes, pieces, data_len=None, parity_only=False, stream=None)
+        segs, pieces   one buffer per segment, nstripes a sequence: a stripe count per segment
     rebuild_segments(nums, piece_ptrs, nstripes, out, nseg=1, piece_seg_stride=0,
                      out_seg_stride=0, stream=None)
         out    [nseg][nstripes][k][ess]
@@ -472,6 +474,35 @@ class SegmentCodec:
         flags = N.EC_FLAG_PARITY_ONLY if parity_only else 0
         rc = self._lib.ec_encode_segments(self.scheme.ctx, self._addr(segs), nseg, nstripes, self._addr(pieces),
                                           flags, self._stream(stream))
+        _raise(self.scheme.ctx, rc)
+
+    def encode_segments_sized(self, segs, nstripes, pieces, data_len=None, parity_only: bool = False, stream=None):
+        """encode_segments with a stripe count per segment
+        (ec_encode_segments_sized): the uploads in flight at once differ in size
+        (single.go:233-238), and one stream-ordered pass serves them all.
+        segs[g] is [nstripes[g]][k][ess], pieces[g] [n][nstripes[g]*ess]
+        ([n-k][...] when parity_only).  With data_len, segment g holds
+        data_len[g] bytes and PadReader's padding is written behind them before
+        the encode.  nstripes[g] == 0 skips segment g (its buffers may be None).
+        Asynchronous on `stream`."""
+        nstripes = [int(x) for x in nstripes]
+        segs, pieces = list(segs), list(pieces)
+        if len(segs) != len(nstripes) or len(pieces) != len(nstripes):
+            raise ValueError("one segment, one stripe count and one piece buffer per segment")
+        if any(x < 0 for x in nstripes):
+            raise ValueError("a stripe count is negative")
+        nseg = len(nstripes)
+        c_len = None
+        if data_len is not None:
+            data_len = [int(x) for x in data_len]
+            if len(data_len) != nseg or any(x < 0 for x in data_len):
+                raise ValueError("one non-negative data length per segment")
+            c_len = (ctypes.c_size_t * max(nseg, 1))(*data_len)
+        c_segs = (ctypes.c_void_p * max(nseg, 1))(*[0 if x is None else self._addr(x) for x in segs])
+        c_out = (ctypes.c_void_p * max(nseg, 1))(*[0 if x is None else self._addr(x) for x in pieces])
+        rc = self._lib.ec_encode_segments_sized(self.scheme.ctx, nseg, c_segs, (ctypes.c_size_t * max(nseg, 1))(*nstripes),
+                                                c_len, c_out, N.EC_FLAG_PARITY_ONLY if parity_only else 0,
+                                                self._stream(stream))
         _raise(self.scheme.ctx, rc)
 
     def decode_segments(self, nums: Iterable[int], piece_ptrs: Iterable[int], nstripes: int, out, nseg: int = 1,

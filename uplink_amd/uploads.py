@@ -1,0 +1,65 @@
+"""A batch of concurrent uploads of different sizes encoded in one call
+(include/uplink_ec.h ec_encode_segments_sized): the counterpart of downloads.py.
+
+What it stands in for: the upload of one segment (private/storage/streams/
+single.go:233-238) wraps the segment's reader in encryption.PadReader for the
+erasure scheme's stripe size and hands it to the encoder, which reads the n
+pieces of that one segment (segmentupload/encode.go:39-75).  Many such uploads
+are in flight at once, of as many sizes as there are objects.  Here they are one
+stream-ordered pass on the GPU.
+
+  upload_geometry   (padded_size, piece_size, nstripes) of an upload
+  encode_uploads    the pieces of a batch of uploads
+"""
+from __future__ import annotations
+
+from typing import Sequence, Tuple
+
+from .eestream import SegmentCodec
+
+
+def upload_geometry(size: int, es) -> Tuple[int, int, int]:
+    """PadReader's sizes of a segment of `size` bytes under erasure scheme `es`
+    (encryption.PadReader: at least 4 bytes of padding, up to whole stripes):
+    (padded_size, piece_size, nstripes)."""
+    if size < 0:
+        raise ValueError("size is negative")
+    stripe = es.stripe_size()
+    padded = size + 4 + (stripe - (size + 4) % stripe) % stripe
+    return padded, padded // es.required_count(), padded // stripe
+
+
+def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only: bool = False, stream=None):
+    """uploads: per upload (size, buffer); `buffer` is a uint8 device tensor of
+    at least padded_size bytes (upload_geometry) whose first `size` bytes are
+    the data.  Its tail is overwritten with PadReader's padding.  Returns per
+    upload a [n, piece_size] device tensor of its pieces ([n-k, piece_size] with
+    parity_only).  A buffer that is too short raises before anything is queued.
+    Asynchronous on `stream`."""
+    import torch
+
+    codec = SegmentCodec(scheme)
+    rows = scheme.total_count() - (scheme.required_count() if parity_only else 0)
+    geo = []
+    for size, buf in uploads:
+        padded, piece_size, ns = upload_geometry(int(size), scheme)
+        if buf.dtype != torch.uint8 or not buf.is_contiguous():
+            raise ValueError("an upload's buffer is a contiguous uint8 tensor")
+        if buf.numel() < padded:
+            raise ValueError(f"an upload of {int(size)} bytes needs a buffer of {padded} bytes, got {buf.numel()}")
+        geo.append((int(size), piece_size, ns, buf))
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        # one allocation per upload: each is 16-byte aligned, so every segment stays in the pass
+        outs = [torch.empty((rows, piece_size), dtype=torch.uint8, device=buf.device) for _, piece_size, _, buf in geo]
+        codec.encode_segments_sized([g[3] for g in geo], [g[2] for g in geo], outs, data_len=[g[0] for g in geo],
+                                    parity_only=parity_only, stream=stream)
+    return outs
+
+
+class _Null:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
