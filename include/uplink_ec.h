@@ -39,6 +39,9 @@
  *   ec_*blake3* / ec_hash_segments / ec_encode_segments_host_hashed
  *                            BLAKE3 piece hash of the upload (piecestore/upload.go:
  *                            133,155,270; hash.go:20-26), SURVEY §8f row 4
+ *   ec_blake3_pieces_list / ec_hash_segments_sized
+ *                            the same with a length per piece: the hashes of a batch of
+ *                            uploads of different sizes in one pass
  *   ec_gcm_*                 AES-256-GCM segment encryption: splitter/splitter.go:156,170
  *                            (upload), streams/store.go:347-382 (download), SURVEY §8f row 4
  *   ec_strerror/ec_format_error  error texts of infectious / eestream
@@ -380,6 +383,49 @@ int ec_blake3_pieces(const uint8_t *base, size_t npieces, long long piece_stride
  * output).  hashes: [nseg][n][32] device bytes.  Async on stream. */
 int ec_hash_segments(const ec_ctx *ctx, const uint8_t *segs, const uint8_t *parity, size_t nseg, size_t nstripes,
                      uint8_t *hashes, ec_stream stream);
+/* ---- a length per piece (the hashes of a batch of uploads of different sizes) ----
+ * Every piece that goes to a storage node is sent with its hash
+ * (piecestore/upload.go:133,155,270), and the uploads in flight at once are of
+ * as many sizes as there are objects (single.go:233-238): these two calls hash
+ * the pieces of such a batch in one stream-ordered pass, where the calls above
+ * take one piece length per call.  One workgroup per 256 KiB of a piece finds
+ * its piece through a per-pass map; a piece of up to 256 KiB is finished there,
+ * a piece of up to 64 MiB by one more workgroup of a second launch.  A piece
+ * whose address and runs allow 16-byte loads takes them whatever the rest of the
+ * list looks like (a pass is at most two chunk launches, one per kind, and one
+ * parents launch); a piece of more than 64 MiB goes on its own through
+ * ec_blake3_pieces' path; same bytes out.  Descriptors, maps and tree nodes are
+ * staged in event-recycled blocks of a pool on the context, long lists go in
+ * passes of bounded staging, and no caller memory is retained after return.
+ * Everything is validated before anything is queued: on an argument error
+ * nothing is written.  Async on stream, no host synchronisation once the pool
+ * is warm.  Not under stream capture (EC_ERR_UNSUPPORTED). */
+
+/* BLAKE3-256 of npieces contiguous device pieces, piece i at pieces[i] with
+ * lens[i] bytes; hashes: npieces*32 device bytes, row i = piece i.
+ * lens[i] == 0 gives the hash of the empty input, and pieces[i] may then be
+ * NULL; a NULL pieces[i] with lens[i] > 0: EC_ERR_INVALID_ARG.  NULL hashes,
+ * pieces or lens with npieces > 0: EC_ERR_INVALID_ARG.  npieces == 0: EC_OK,
+ * nothing queued. */
+int ec_blake3_pieces_list(const ec_ctx *ctx, size_t npieces, const uint8_t *const *pieces, const size_t *lens,
+                          uint8_t *hashes, ec_stream stream);
+/* All n piece hashes of a batch encoded by ec_encode_segments_sized: same
+ * segs / nstripes / pieces / flags as that call.  hashes: [nseg][n][32] device.
+ * Without EC_FLAG_PARITY_ONLY pieces[g] is [n][nstripes[g]*ess] and all n rows
+ * are hashed from it; segs may be NULL.  With EC_FLAG_PARITY_ONLY pieces[g] is
+ * [n-k][...] and data piece j is read from segs[g] in place (runs of ess bytes,
+ * k*ess apart, as ec_hash_segments reads it): segs[g] is required.
+ * nstripes[g] == 0 skips segment g: nothing of it is read, its pointers may be
+ * NULL and its n*32 hash bytes are left untouched.  A NULL pointer of a segment
+ * that is not skipped: EC_ERR_INVALID_ARG. */
+int ec_hash_segments_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *const *segs, const size_t *nstripes,
+                           const uint8_t *const *pieces, int flags, uint8_t *hashes, ec_stream stream);
+/* Launches of the two calls above on this ctx so far (a diagnostic): chunk
+ * launches over pieces read with 16-byte loads, chunk launches over pieces read
+ * byte by byte, parents launches, and pieces of more than 64 MiB sent through
+ * ec_blake3_pieces' path.  Any pointer may be NULL.  No reference counterpart. */
+int ec_hash_list_stats(const ec_ctx *ctx, unsigned long long *fast, unsigned long long *bytewise,
+                       unsigned long long *parents, unsigned long long *oversize);
 /* Host buffers, synchronous: hashes[32*j] = BLAKE3(data + j*stride, piece_len) */
 int ec_blake3_host(const uint8_t *data, size_t npieces, long long stride, size_t piece_len, uint8_t *hashes);
 

@@ -49,11 +49,41 @@ __device__ __forceinline__ const uint8_t *at(const B3View &v, const uint8_t *pb,
     return pb + (int64_t)(t / v.run) * v.run_stride + (t % v.run);
 }
 
+// Checked build, list kernels (v.chk_flag set): `bytes` at p lie in the piece's
+// own extent -- [pb, pb + len) of a contiguous piece, run r of a strided one at
+// [pb + r*run_stride, + run) -- else the access is skipped and its site recorded.
+// In the product build this is `true` and compiles away.
+__device__ __forceinline__ bool in_piece(const B3View &v, const uint8_t *pb, const uint8_t *p, uint32_t bytes,
+                                         int site) {
+#ifdef UPLINK_EC_CHECKED
+    if (!v.chk_flag) return true;
+    const int64_t off = p - pb;
+    bool ok = off >= 0;
+    if (ok && v.run_stride <= 0) ok = (uint64_t)off + bytes <= v.piece_len;
+    if (ok && v.run_stride > 0) {
+        const uint64_t r = (uint64_t)off / (uint64_t)v.run_stride, w = (uint64_t)off % (uint64_t)v.run_stride;
+        ok = w + bytes <= v.run && r * v.run + w + bytes <= v.piece_len;
+    }
+    if (!ok) atomicCAS(v.chk_flag, 0u, (uint32_t)site);
+    return ok;
+#else
+    (void)v, (void)pb, (void)p, (void)bytes, (void)site;
+    return true;
+#endif
+}
+constexpr int kSiteLines = 31, kSiteBlock = 32, kSiteByte = 33, kSiteNodeLoad = 34, kSiteNodeStore = 35,
+              kSiteHash = 36;  // (checked build)
+
 // `n` 16-byte words at p (plain loads: the second half of each 128-byte
 // line is read by the next block, so non-temporal loads, which let the line
 // go, cost 2x here -- tools/exp/b3_probe.hip)
 template <int n>
-__device__ __forceinline__ void load_words(const uint8_t *p, uint32_t *m) {
+__device__ __forceinline__ void load_words(const B3View &v, const uint8_t *pb, const uint8_t *p, uint32_t *m) {
+    if (!in_piece(v, pb, p, 16 * n, n == 8 ? kSiteLines : kSiteBlock)) {
+#pragma unroll
+        for (int i = 0; i < 4 * n; i++) m[i] = 0;
+        return;
+    }
     const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
 #pragma unroll
     for (int i = 0; i < n; i++) {
@@ -67,12 +97,15 @@ template <bool kFast>
 __device__ __forceinline__ void load_block(const B3View &v, const uint8_t *pb, uint64_t t, uint32_t len,
                                            uint32_t (&m)[16]) {
     if (kFast && len == 64) {  // the block lies in one run, 16-byte aligned
-        load_words<4>(at<kFast>(v, pb, t), m);
+        load_words<4>(v, pb, at<kFast>(v, pb, t), m);
         return;
     }
 #pragma unroll
     for (int i = 0; i < 16; i++) m[i] = 0;
-    for (uint32_t b = 0; b < len; b++) m[b >> 2] |= (uint32_t)*at<kFast>(v, pb, t + b) << (8 * (b & 3));
+    for (uint32_t b = 0; b < len; b++) {
+        const uint8_t *p = at<kFast>(v, pb, t + b);
+        if (in_piece(v, pb, p, 1, kSiteByte)) m[b >> 2] |= (uint32_t)*p << (8 * (b & 3));
+    }
 }
 
 // CV of a full 1 KiB chunk whose 128-byte lines each lie in one run: one
@@ -80,9 +113,9 @@ __device__ __forceinline__ void load_block(const B3View &v, const uint8_t *pb, u
 __device__ __forceinline__ void full_chunk_lines(const B3View &v, const uint8_t *pb, uint64_t t0, uint64_t c,
                                                  uint32_t last_flags, uint32_t (&h)[8]) {
     uint32_t m[32], nx[32];
-    load_words<8>(at<true>(v, pb, t0), m);
+    load_words<8>(v, pb, at<true>(v, pb, t0), m);
     for (int pr = 0; pr < 8; pr++) {
-        if (pr < 7) load_words<8>(at<true>(v, pb, t0 + 128 * (pr + 1)), nx);
+        if (pr < 7) load_words<8>(v, pb, at<true>(v, pb, t0 + 128 * (pr + 1)), nx);
         uint32_t lo[16], hi[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) lo[i] = m[i], hi[i] = m[16 + i];
@@ -222,6 +255,110 @@ __global__ __launch_bounds__(kGroup) void b3_parents(const uint32_t *nodes_in, u
     }
 }
 
+// ---- a list of pieces, each with its own length (blake3.hpp B3ListPass) ----
+// b3_chunks_list: one workgroup per aligned group of 256 chunks of one piece, as
+//     b3_chunks; the workgroup finds its piece through the launch's map (one uint32
+//     per workgroup, wave-uniform: the descriptor comes in through scalar loads) and
+//     builds the piece's view in registers.  A piece of one group is finished here
+//     (one chunk and the empty piece: ROOT on the last block); a larger one leaves
+//     its group CVs in its node slots.
+// b3_parents_list: one workgroup per piece of 2..256 groups folds the piece's
+//     nodes and writes the root.
+// Kernel arguments of both.
+struct B3ListArgs {
+    const B3ListDesc *desc;
+    const uint32_t *map;  // [workgroup] -> position of its piece's descriptor
+    uint32_t *nodes;
+    uint32_t node_cap;
+    uint8_t *hash_lo, *hash_hi;  // checked build: the declared range of the hash stores
+    uint32_t *chk_flag;
+};
+
+// Checked build: a hash or node store compared with its declared range.
+__device__ __forceinline__ bool list_store_ok(const B3ListArgs &a, const void *p, bool node, int site) {
+#ifdef UPLINK_EC_CHECKED
+    const uint8_t *q = static_cast<const uint8_t *>(p);
+    const uint8_t *lo = node ? reinterpret_cast<const uint8_t *>(a.nodes) : a.hash_lo;
+    const uint8_t *hi = node ? lo + 32ull * a.node_cap : a.hash_hi;
+    if (q < lo || q + 32 > hi) {
+        if (a.chk_flag) atomicCAS(a.chk_flag, 0u, (uint32_t)site);
+        return false;
+    }
+#else
+    (void)a, (void)p, (void)node, (void)site;
+#endif
+    return true;
+}
+
+template <bool kFast>
+__global__ __launch_bounds__(kGroup) void b3_chunks_list(B3ListArgs a) {
+    __shared__ uint32_t lds[2][8][kGroup];
+    const B3ListDesc d = a.desc[a.map[blockIdx.x]];
+    const uint32_t group = blockIdx.x - d.wg0;
+    B3View v{};
+    v.base = d.base, v.piece_len = d.len, v.run = d.run, v.run_stride = d.run_stride, v.run_shift = d.run_shift;
+    v.npieces = v.pieces_per_set = 1;
+#ifdef UPLINK_EC_CHECKED
+    v.chk_flag = a.chk_flag;
+#endif
+    const uint64_t nchunks = d.len ? (d.len - 1) / 1024 + 1 : 1;
+    if (nchunks == 1) {  // the whole piece is lane 0's: it also applies ROOT
+        if (threadIdx.x == 0) {
+            uint32_t h[8];
+            chunk_cv<kFast>(v, d.base, 0, true, h);
+            if (list_store_ok(a, d.hash, false, kSiteHash)) store_hash(d.hash, h);
+        }
+        return;
+    }
+    const uint64_t c0 = (uint64_t)group * kGroup + threadIdx.x;
+    if (c0 < nchunks) {
+        uint32_t h[8];
+        chunk_cv<kFast>(v, d.base, c0, false, h);
+#pragma unroll
+        for (int i = 0; i < 8; i++) lds[0][i][threadIdx.x] = h[i];
+    }
+    __syncthreads();
+    const uint64_t left = nchunks - (uint64_t)group * kGroup;  // chunks in this group
+    const int cnt = left < (uint64_t)kGroup ? (int)left : kGroup;
+    uint32_t h[8];
+    fold(lds, cnt, d.groups == 1, h);
+    if (threadIdx.x == 0) {
+        if (d.groups == 1) {
+            if (list_store_ok(a, d.hash, false, kSiteHash)) store_hash(d.hash, h);
+        } else {
+            uint4 *o = reinterpret_cast<uint4 *>(a.nodes + ((uint64_t)d.node0 + group) * 8);
+            if (list_store_ok(a, o, true, kSiteNodeStore)) {
+                o[0] = make_uint4(h[0], h[1], h[2], h[3]);
+                o[1] = make_uint4(h[4], h[5], h[6], h[7]);
+            }
+        }
+    }
+}
+
+// a.map: the pass's pieces of 2..256 groups, one workgroup each
+__global__ __launch_bounds__(kGroup) void b3_parents_list(B3ListArgs a) {
+    __shared__ uint32_t lds[2][8][kGroup];
+    const B3ListDesc d = a.desc[a.map[blockIdx.x]];
+    const int cnt = (int)d.groups;
+    if ((int)threadIdx.x < cnt) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(a.nodes + ((uint64_t)d.node0 + threadIdx.x) * 8);
+        uint4 x = make_uint4(0, 0, 0, 0), y = x;
+        if (list_store_ok(a, p, true, kSiteNodeLoad)) x = p[0], y = p[1];
+        lds[0][0][threadIdx.x] = x.x, lds[0][1][threadIdx.x] = x.y, lds[0][2][threadIdx.x] = x.z;
+        lds[0][3][threadIdx.x] = x.w, lds[0][4][threadIdx.x] = y.x, lds[0][5][threadIdx.x] = y.y;
+        lds[0][6][threadIdx.x] = y.z, lds[0][7][threadIdx.x] = y.w;
+    }
+    __syncthreads();
+    uint32_t h[8];
+    fold(lds, cnt, true, h);
+    if (threadIdx.x == 0 && list_store_ok(a, d.hash, false, kSiteHash)) store_hash(d.hash, h);
+}
+
+// The pass's staging from the host's pinned memory to device memory, 16 bytes per lane.
+__global__ __launch_bounds__(256) void b3_list_stage(const uint4 *src, uint4 *dst, uint32_t n16) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
 // Streamed hashing (ec_upload with EC_FLAG_HASH_PIECES): the CVs of chunks
 // [c0, c1) of every piece, written to cvs[piece][c][8] of pieces of nchunks
 // >= 2 chunks (so no chunk is the root), one lane per chunk.  Once every range
@@ -343,6 +480,33 @@ hipError_t b3_launch_fold(uint32_t *cvs, uint64_t npieces, uint64_t nchunks, uin
         uint32_t *t = a;
         a = b;
         b = t;
+    }
+    return e;
+}
+
+hipError_t b3_launch_list(const B3ListPass &p, hipStream_t stream) {
+    if (p.wgs_fast == 0 && p.wgs_byte == 0) return hipSuccess;
+    if (!p.h_stage || !p.d_stage || !p.desc || (p.stage_bytes & 15) || (p.nparents && !p.nodes))
+        return hipErrorInvalidValue;
+    const uint32_t n16 = (uint32_t)(p.stage_bytes / 16);
+    const uint32_t copy_wgs = (n16 + 255) / 256 < 64 ? (n16 + 255) / 256 : 64;
+    b3_list_stage<<<dim3(copy_wgs), 256, 0, stream>>>(static_cast<const uint4 *>(p.h_stage),
+                                                       static_cast<uint4 *>(p.d_stage), n16);
+    hipError_t e = hipGetLastError();
+    B3ListArgs a{p.desc, p.map_fast, p.nodes, p.node_cap, p.hash_lo, p.hash_hi, p.chk_flag};
+    if (e == hipSuccess && p.wgs_fast) {
+        b3_chunks_list<true><<<dim3(p.wgs_fast), kGroup, 0, stream>>>(a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && p.wgs_byte) {
+        a.map = p.map_byte;
+        b3_chunks_list<false><<<dim3(p.wgs_byte), kGroup, 0, stream>>>(a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && p.nparents) {
+        a.map = p.parents;
+        b3_parents_list<<<dim3(p.nparents), kGroup, 0, stream>>>(a);
+        e = hipGetLastError();
     }
     return e;
 }

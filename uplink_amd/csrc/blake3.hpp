@@ -24,7 +24,50 @@ struct B3View {
     uint64_t pieces_per_set;
     int64_t set_stride;
     int32_t run_shift;  // set by b3_launch: log2(run) when run is a power of two, else -1
+#ifdef UPLINK_EC_CHECKED
+    // checked build, list kernels: every load is compared with the piece's own
+    // extent and a violation's site recorded here (nullptr: the uniform launches, unchecked)
+    uint32_t *chk_flag;
+#endif
 };
+
+// ---- a list of pieces that each have their own length (ec_blake3_pieces_list,
+// ec_hash_segments_sized; geometry in b3_list_geom.hpp) ----
+// One piece of a pass, in device memory: byte t at base + (t >> run_shift)*run_stride
+// + (t & (run - 1)) on the fast path, base + (t / run)*run_stride + t % run on the
+// byte path (a contiguous piece: run = 2^62, run_stride = 0).
+struct B3ListDesc {
+    const uint8_t *base;
+    uint64_t len;
+    uint64_t run;
+    int64_t run_stride;
+    uint8_t *hash;     // where its 32 bytes go
+    uint32_t wg0;      // its first workgroup in its launch (the fast or the byte pieces')
+    uint32_t node0;    // its first node slot (pieces of >= 2 groups)
+    uint32_t groups;   // its 256-chunk groups: 1 .. 256
+    int32_t run_shift;
+    uint64_t rsv;
+};
+static_assert(sizeof(B3ListDesc) == 64, "staged as 16-byte words");
+
+// One pass: `stage_bytes` of host-written staging (descriptors, the two launches'
+// workgroup -> piece maps, the parents list) at h_stage are copied to d_stage by a
+// kernel, and desc / map_* / parents point into d_stage.  Then at most two chunk
+// launches (fast and byte pieces) and one parents launch, stream-ordered.
+struct B3ListPass {
+    const void *h_stage;  // pinned, 16-byte aligned
+    void *d_stage;
+    size_t stage_bytes;   // a multiple of 16
+    const B3ListDesc *desc;
+    const uint32_t *map_fast, *map_byte, *parents;
+    uint32_t wgs_fast, wgs_byte, nparents;
+    uint32_t *nodes;      // node scratch, node_cap slots of 32 bytes
+    uint32_t node_cap;
+    // checked build: the declared range of the hash stores and the violation word
+    uint8_t *hash_lo, *hash_hi;
+    uint32_t *chk_flag;
+};
+hipError_t b3_launch_list(const B3ListPass &p, hipStream_t stream);
 
 // Device bytes of scratch b3_launch needs for this view (0 when every piece
 // fits one 256-chunk group).

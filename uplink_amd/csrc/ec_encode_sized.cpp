@@ -21,6 +21,8 @@ size_t pow2_at_least(size_t n, size_t lo) {
 
 size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+}  // namespace
+
 // A block of the context's pool with room for h_need pinned and d_need device
 // bytes whose previous pass has finished on the GPU, or a new one (sized in
 // powers of two).  nullptr: no memory.  (RepairBlock's mechanism, ec_repair.cpp;
@@ -73,6 +75,8 @@ void block_release(RepairPool &P, RepairBlock *b, bool launched, hipStream_t s) 
     b->queued = launched;
     b->busy = false;
 }
+
+namespace {
 
 // One segment the sized kernel takes.
 struct EncSeg {

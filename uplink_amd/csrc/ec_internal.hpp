@@ -494,6 +494,10 @@ struct ec_ctx {
     // sets_merge does for the share-set calls): the A/B of DESIGN.md §4h
     bool sized_merge = false;
     RepairPool enc_sized;  // staging of ec_encode_segments_sized (ec_encode_sized.cpp): a pool of its own
+    RepairPool hash_sized;  // staging of ec_blake3_pieces_list / ec_hash_segments_sized (ec_hash_sized.cpp)
+    // launches of those two calls so far: fast chunk launches, byte chunk launches, parents
+    // launches, oversize pieces sent through the uniform launch (ec_hash_list_stats)
+    std::atomic<uint64_t> hl_fast{0}, hl_byte{0}, hl_parents{0}, hl_oversize{0};
     SlBuilder slb;
 };
 
@@ -547,6 +551,12 @@ B3View parity_view(const ec_ctx *c, const uint8_t *parity, size_t nseg, size_t n
 size_t b3_segment_ws_bytes(const ec_ctx *c, size_t nseg, size_t nstripes);
 int hash_segments(const ec_ctx *c, const uint8_t *segs, const uint8_t *parity, size_t nseg, size_t nstripes,
                   uint8_t *hashes, uint8_t *ws, hipStream_t st);
+
+// ec_encode_sized.cpp: a block of pool P with room for h_need pinned and d_need device bytes
+// whose previous pass has finished on the GPU, or a new one (nullptr: no memory); and its
+// return, `launched` when something that reads it was queued on s
+RepairBlock *block_acquire(RepairPool &P, size_t h_need, size_t d_need);
+void block_release(RepairPool &P, RepairBlock *b, bool launched, hipStream_t s);
 
 // ec_sets.cpp
 void stop_builder(ec_ctx *c);  // stop and join the context's straight-line builder (ec_destroy)

@@ -11,7 +11,10 @@ The reference hashes each piece while it streams to the storage node, one
 byte slice at a time.  Here the hash of every piece of a segment is computed
 by the GPU next to the encode, from the copies the encoder already has in
 HBM (ec_hash_segments / ec_encode_segments_host_hashed), and the uploader
-sends the precomputed 32 bytes.  BLAKE3 is the only algorithm the engine
+sends the precomputed 32 bytes.  Pieces that each have their own length --
+the uploads in flight at once are of as many sizes as objects -- are hashed
+in one pass by blake3_pieces_list / hash_segments_sized
+(ec_blake3_pieces_list / ec_hash_segments_sized).  BLAKE3 is the only algorithm the engine
 computes: SHA-256 (the legacy option) is sequential within a piece and is
 left to the caller, so asking for it raises.
 """
@@ -76,3 +79,78 @@ def hash_segments(scheme, segs, parity, nseg: int, nstripes: int, hashes, stream
                                    SegmentCodec._addr(parity) if parity is not None else None, nseg, nstripes,
                                    SegmentCodec._addr(hashes), SegmentCodec._stream(stream))
     _raise(scheme.ctx, rc)
+
+
+def _ctx_of(scheme_or_ctx):
+    return scheme_or_ctx.ctx if hasattr(scheme_or_ctx, "ctx") else scheme_or_ctx
+
+
+def blake3_pieces_list(scheme_or_ctx, tensors, hashes=None, stream=None, algo=DEFAULT_ALGORITHM):
+    """ec_blake3_pieces_list: BLAKE3 of a list of contiguous uint8 device
+    tensors of any lengths (an empty one hashes the empty input), in one
+    stream-ordered pass.  Returns the [npieces, 32] device tensor of their
+    hashes, row i for tensors[i] (`hashes` when given).  Asynchronous on
+    `stream`; the tensors must stay alive until the stream has run the call."""
+    _check(algo)
+    import torch
+
+    from .eestream import SegmentCodec
+    tensors = list(tensors)
+    for t in tensors:
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("a piece is a contiguous uint8 tensor")
+    npieces = len(tensors)
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    if hashes is None:
+        dev = tensors[0].device if tensors else "cuda"
+        with torch.cuda.stream(ts) if ts is not None else _Null():
+            hashes = torch.empty((npieces, 32), dtype=torch.uint8, device=dev)
+    elif hashes.numel() != npieces * 32 or hashes.dtype != torch.uint8 or not hashes.is_contiguous():
+        raise ValueError("hashes is a contiguous uint8 tensor of npieces*32 bytes")
+    ctx = _ctx_of(scheme_or_ctx)
+    c_ptrs = (ctypes.c_void_p * max(npieces, 1))(*[t.data_ptr() if t.numel() else None for t in tensors])
+    c_lens = (ctypes.c_size_t * max(npieces, 1))(*[t.numel() for t in tensors])
+    rc = N.load().ec_blake3_pieces_list(ctx, npieces, c_ptrs, c_lens, hashes.data_ptr() if npieces else None,
+                                        SegmentCodec._stream(stream))
+    _raise(ctx, rc)
+    return hashes
+
+
+def hash_segments_sized(scheme_or_ctx, segs, nstripes, pieces, hashes, parity_only: bool = False, stream=None,
+                        algo=DEFAULT_ALGORITHM):
+    """ec_hash_segments_sized: all n piece hashes of a batch encoded by
+    ec_encode_segments_sized, from the same segs / nstripes / pieces /
+    parity_only.  hashes [nseg][n][32] on the device.  With parity_only the data
+    pieces are read in place from the stripe-major segments; without it segs may
+    be None.  nstripes[g] == 0 skips segment g (its buffers may be None, its hash
+    rows stay as they are).  Asynchronous on `stream`."""
+    _check(algo)
+    from .eestream import SegmentCodec
+    nstripes = [int(x) for x in nstripes]
+    nseg = len(nstripes)
+    pieces = list(pieces)
+    segs = None if segs is None else list(segs)
+    if len(pieces) != nseg or (segs is not None and len(segs) != nseg):
+        raise ValueError("one segment, one stripe count and one piece buffer per segment")
+    if any(x < 0 for x in nstripes):
+        raise ValueError("a stripe count is negative")
+    if parity_only and segs is None:
+        raise ValueError("parity_only reads the data pieces from the segments")
+
+    def arr(xs):
+        return (ctypes.c_void_p * max(nseg, 1))(*[None if x is None else SegmentCodec._addr(x) for x in xs])
+
+    ctx = _ctx_of(scheme_or_ctx)
+    rc = N.load().ec_hash_segments_sized(ctx, nseg, None if segs is None else arr(segs),
+                                         (ctypes.c_size_t * max(nseg, 1))(*nstripes), arr(pieces),
+                                         N.EC_FLAG_PARITY_ONLY if parity_only else 0, SegmentCodec._addr(hashes),
+                                         SegmentCodec._stream(stream))
+    _raise(ctx, rc)
+
+
+class _Null:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False

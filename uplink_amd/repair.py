@@ -130,12 +130,14 @@ def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces
                     _raise(ctx, N.EC_ERR_TOO_MANY_ERRORS)
         if not hash_pieces:
             return outs
-        hashes = [torch.empty((o.shape[0], 32), dtype=torch.uint8, device=dev) for o in outs]
-        for o, h in zip(outs, hashes):
-            if o.shape[0]:
-                rc = lib.ec_blake3_pieces(o.data_ptr(), o.shape[0], plen, plen, 0, 0, h.data_ptr(),
-                                          SegmentCodec._stream(stream))
-                _raise(ctx, rc)
+        # every regenerated row in one list call: they have one length and differ in where they lie
+        from .piecehash import blake3_pieces_list
+        flat = blake3_pieces_list(ctx, rows, stream=stream) if rows else None
+        hashes, at = [], 0
+        for o in outs:
+            cnt = o.shape[0]
+            hashes.append(flat[at:at + cnt] if cnt else torch.empty((0, 32), dtype=torch.uint8, device=dev))
+            at += cnt
         return outs, hashes
 
 

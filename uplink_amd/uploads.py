@@ -9,7 +9,8 @@ are in flight at once, of as many sizes as there are objects.  Here they are one
 stream-ordered pass on the GPU.
 
   upload_geometry   (padded_size, piece_size, nstripes) of an upload
-  encode_uploads    the pieces of a batch of uploads
+  encode_uploads    the pieces of a batch of uploads and, with hash_pieces, the
+                    BLAKE3 hash each piece is sent with (ec_hash_segments_sized)
 """
 from __future__ import annotations
 
@@ -29,13 +30,19 @@ def upload_geometry(size: int, es) -> Tuple[int, int, int]:
     return padded, padded // es.required_count(), padded // stripe
 
 
-def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only: bool = False, stream=None):
+def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only: bool = False,
+                   hash_pieces: bool = False, stream=None):
     """uploads: per upload (size, buffer); `buffer` is a uint8 device tensor of
     at least padded_size bytes (upload_geometry) whose first `size` bytes are
     the data.  Its tail is overwritten with PadReader's padding.  Returns per
     upload a [n, piece_size] device tensor of its pieces ([n-k, piece_size] with
     parity_only).  A buffer that is too short raises before anything is queued.
-    Asynchronous on `stream`."""
+    With hash_pieces it returns (pieces, hashes): hashes[g] is the [n, 32]
+    device tensor of the BLAKE3 hashes upload g's pieces are sent with
+    (piecestore/upload.go:270), all n rows also with parity_only (the data
+    pieces are then hashed in place from the padded buffer); the rows are views
+    of one buffer, filled by one ec_hash_segments_sized call queued behind the
+    encode.  Asynchronous on `stream`."""
     import torch
 
     codec = SegmentCodec(scheme)
@@ -54,7 +61,13 @@ def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only
         outs = [torch.empty((rows, piece_size), dtype=torch.uint8, device=buf.device) for _, piece_size, _, buf in geo]
         codec.encode_segments_sized([g[3] for g in geo], [g[2] for g in geo], outs, data_len=[g[0] for g in geo],
                                     parity_only=parity_only, stream=stream)
-    return outs
+        if not hash_pieces:
+            return outs
+        dev = geo[0][3].device if geo else "cuda"
+        hashes = torch.empty((len(geo), scheme.total_count(), 32), dtype=torch.uint8, device=dev)
+        codec.hash_segments_sized([g[3] for g in geo], [g[2] for g in geo], outs, hashes, parity_only=parity_only,
+                                  stream=stream)
+    return outs, [hashes[g] for g in range(len(geo))]
 
 
 class _Null:
