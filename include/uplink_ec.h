@@ -44,6 +44,9 @@
  *                            uploads of different sizes in one pass
  *   ec_gcm_*                 AES-256-GCM segment encryption: splitter/splitter.go:156,170
  *                            (upload), streams/store.go:347-382 (download), SURVEY §8f row 4
+ *   ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized
+ *                            the same with a block count, key and nonce per segment: the
+ *                            cipher of a batch of different sizes in one pass
  *   ec_strerror/ec_format_error  error texts of infectious / eestream
  *
  * Error codes map to the errors eestream's callers test:
@@ -460,6 +463,57 @@ int ec_gcm_seal_segments_strided(const uint8_t *plain, long long plain_seg_strid
 int ec_gcm_open_segments_strided(const uint8_t *cipher, long long cipher_seg_stride, size_t nseg, size_t nblocks,
                                  size_t in_block, const void *dev_keys, const uint8_t *dev_nonces, uint8_t *out,
                                  long long out_seg_stride, int32_t *dev_status, ec_stream stream);
+/* ---- a size per segment (the cipher of a batch of uploads or downloads of different sizes) ----
+ * The upload seals each segment through TransformWriterPadded(NewEncrypter(...))
+ * (splitter/splitter.go:156,170) and the download opens it through decryptRanger
+ * (streams/store.go:347-382), each from its own length, key and nonce; the
+ * segments in flight at once are of as many sizes as there are objects.  These
+ * two calls run the cipher over such a batch in one stream-ordered pass, where
+ * the calls above take one nblocks per call.  Segment g is nblocks[g] dense GCM
+ * blocks: sealing reads in_block plaintext bytes per block from plain[g] and
+ * writes ciphertext || tag (in_block + 16 bytes per block) to out[g]; opening
+ * does the reverse.  Segment g uses prepared key g of dev_keys
+ * (ec_gcm_key_bytes() apart) and nonce dev_nonces[12*g..], block b sealed under
+ * nonce + b: the same bytes as ec_gcm_seal_segments / ec_gcm_open_segments on
+ * each segment alone.  A segment's input and output must not overlap each other
+ * or another segment's (the caller's to ensure).  Every segment gets workgroups
+ * in proportion to its blocks, at least one and at most one per four blocks, out
+ * of the grid the uniform call aims for; a workgroup finds its segment through a
+ * per-pass map.  ctx supplies only the device and a staging pool: descriptors
+ * and maps are staged in event-recycled blocks, long lists go in passes of at
+ * most 4096 segments, and no caller memory is retained after return.
+ * nblocks[g] == 0 skips segment g: nothing of it is read or written and its
+ * pointers may be NULL (the open call still writes dev_status[g] = -1).
+ * Everything is validated before anything is queued: on an argument error
+ * nothing is written.  EC_ERR_INVALID_ARG: NULL ctx, a NULL array with nseg > 0,
+ * NULL dev_keys or dev_nonces, NULL dev_status (open), a NULL pointer of a
+ * segment that is not skipped, a data_len that does not pad to nblocks.
+ * EC_ERR_UNSUPPORTED: in_block 0, above 1<<24 or no multiple of 16, a pointer
+ * of a segment that is not skipped that is not 16-byte aligned, nblocks[g] above
+ * 0x7FFFFFFF, nseg above 0xFFFFFFFF, a capturing stream.  nseg == 0: EC_OK,
+ * nothing queued.  Async on stream, no host synchronisation once the pool is
+ * warm. */
+
+/* data_len NULL: the plaintext is already padded and is only read.  Otherwise
+ * segment g holds data_len[g] bytes and the call writes PadReader's padding to
+ * in_block behind them, in stream order before the seal -- the bytes
+ * ec_pad_segments(plain[g], 1, 0, data_len[g], in_block, stream) writes -- and
+ * requires nblocks[g]*in_block == data_len[g] + p,
+ * p = 4 + (in_block - (data_len[g]+4) % in_block) % in_block. */
+int ec_gcm_seal_segments_sized(const ec_ctx *ctx, size_t nseg, uint8_t *const *plain, const size_t *nblocks,
+                               const size_t *data_len /* may be NULL */, size_t in_block, const void *dev_keys,
+                               const uint8_t *dev_nonces, uint8_t *const *out, ec_stream stream);
+/* dev_status: [nseg] device; dev_status[g] ends as -1, or as the first block of
+ * segment g whose tag did not verify (its plaintext must not be used).  A
+ * failing segment does not stop the others. */
+int ec_gcm_open_segments_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *const *cipher, const size_t *nblocks,
+                               size_t in_block, const void *dev_keys, const uint8_t *dev_nonces,
+                               uint8_t *const *out, int32_t *dev_status, ec_stream stream);
+/* Cipher launches of the two calls above on this ctx so far (a diagnostic): of
+ * the seal, of the open, and the passes of both.  Any pointer may be NULL.  No
+ * reference counterpart. */
+int ec_gcm_sized_stats(const ec_ctx *ctx, unsigned long long *seal_launches, unsigned long long *open_launches,
+                       unsigned long long *passes);
 /* PadReader padding (single.go:236) on the device: after
  * data_len bytes of each of nseg segments (seg_stride apart) write
  * p = 4 + (block - (data_len+4) % block) % block bytes of byte(p), the last

@@ -35,7 +35,7 @@ def main():
     args = ap.parse_args()
     if args.lib:
         from uplink_amd import _native
-        _native.load(args.lib)  # (the process's library from here on)
+        _native.load(args.lib, partial=True)  # (the process's library from here on; an older build lacks later exports)
     torch.cuda.set_device(0)
     nseg = args.nseg
     rng = np.random.default_rng(3)

@@ -28,6 +28,13 @@
 // H^(64-l) on Shoup's 4-bit tables of H^1..H^64, all in LDS (20 KB per key,
 // built on the host by gcm_prepare).  36.6 KB of LDS and 128 VGPRs per
 // workgroup of 4 waves: four workgroups per CU.
+//
+// Two kernels.  gcm_blocks: segments of one block count, a fixed number of
+// workgroups each (gcm_launch).  gcm_blocks_sized: segments that each have
+// their own block count (ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized);
+// a workgroup finds its segment's descriptor through a per-pass map, and the
+// segment's workgroups run the same stride loop over its blocks
+// (gcm_launch_sized, gcm_sized_geom.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -206,6 +213,140 @@ __device__ __forceinline__ void load_tail(const uint8_t *p, uint32_t n, uint32_t
     for (uint32_t i = 0; i < n; i++) w[i >> 2] |= (uint32_t)p[i] << (24 - 8 * (i & 3));
 }
 
+// What a GCM block's shape fixes for every block of a launch.
+// (in_block a multiple of 16: gcm_block has no short last sub-block)
+struct GcmShape {
+    uint32_t ib;                  // in_block
+    uint32_t slots, steps, pad;   // GHASH inputs (sub-blocks + the length block), Horner steps, leading zero slots
+    uint64_t clen_bits;
+    __device__ __forceinline__ explicit GcmShape(uint32_t in_block)
+        : ib(in_block), slots(in_block / 16 + 1), steps((slots + 63) / 64), pad(steps * 64 - slots),
+          clen_bits((uint64_t)in_block * 8) {}
+};
+
+// AES tables, reduction constants and key ks's GHASH tables into the workgroup's LDS
+__device__ __forceinline__ void gcm_fill_lds(Lds &L, const GcmSched *ks) {
+    for (int i = threadIdx.x; i < 256 * kCopies; i += blockDim.x) L.t[i] = kAesDev.t0[i / kCopies];
+    if (threadIdx.x < 16) L.rem[threadIdx.x] = kRem4[threadIdx.x];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(&ks->htab[0][0][0]);
+        uint4 *dst = reinterpret_cast<uint4 *>(&L.htab[0][0][0]);
+        for (int i = threadIdx.x; i < 64 * 16; i += blockDim.x) dst[i] = src[i];
+        const uint4 *s8 = reinterpret_cast<const uint4 *>(&ks->h64_8[0][0]);
+        uint4 *d8 = reinterpret_cast<uint4 *>(&L.h8[0][0]);
+        for (int i = threadIdx.x; i < 256; i += blockDim.x) {
+            d8[i] = s8[i];
+            L.rem8[i] = kRem8.r[i];
+        }
+    }
+    __syncthreads();
+}
+
+// the segment's nonce as a little-endian 96-bit integer
+__device__ __forceinline__ void gcm_load_nonce(const uint8_t *nonce, uint32_t (&nw)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        nw[i] = (uint32_t)nonce[4 * i] | (uint32_t)nonce[4 * i + 1] << 8 | (uint32_t)nonce[4 * i + 2] << 16 |
+                (uint32_t)nonce[4 * i + 3] << 24;
+}
+
+// One GCM block on one wave: block b of a segment whose nonce is nw, read at src
+// and written at dst, under the key whose round keys are rk and whose tables are
+// in L, in_block a multiple of 16.  The counter blocks, the Horner GHASH with H^64,
+// the final products, the tag and (open) its comparison, as gcm_blocks below has
+// them in its loop; every global access goes through chk.  gcm_blocks keeps its own
+// text: calling this body from it changed its register allocation (scratch 8 / 12
+// bytes per lane became 24 / 28), so only gcm_blocks_sized calls it.
+template <bool kOpen, class Chk>
+__device__ __forceinline__ void gcm_block(const Lds &L, const uint32_t *__restrict__ rk, const uint32_t (&nw)[3],
+                                          uint32_t b, const uint8_t *src, uint8_t *dst, const GcmShape &g, int lane,
+                                          int32_t *status, const Chk &chk) {
+    const uint32_t ib = g.ib, slots = g.slots, steps = g.steps, pad = g.pad;
+    // nonce + b, little-endian with carry across the 12 bytes; then big-endian words for AES
+    uint32_t n0 = nw[0], n1 = nw[1], n2 = nw[2];
+    {
+        const uint64_t lo = (uint64_t)n0 + (uint32_t)b;
+        n0 = (uint32_t)lo;
+        const uint64_t mid = (uint64_t)n1 + (lo >> 32);
+        n1 = (uint32_t)mid;
+        n2 += (uint32_t)(mid >> 32);
+    }
+    const uint32_t j0w0 = bswap(n0), j0w1 = bswap(n1), j0w2 = bswap(n2);
+    uint32_t acc[4] = {0, 0, 0, 0}, ekj0[4] = {0, 0, 0, 0};
+    for (uint32_t j = 0; j < steps; j++) {
+        const uint32_t t = (uint32_t)lane + 64 * j;
+        const bool is_data = t >= pad && t + 1 < pad + slots;
+        const bool is_len = t + 1 == pad + slots;
+        const uint32_t sidx = t - pad;
+        // every lane runs the AES (no divergent second pass): data lanes on their counter block,
+        // padding lanes on J0 (the tag mask), the length-block lane on a value it ignores
+        uint32_t ks4[4] = {j0w0, j0w1, j0w2, is_data ? 2 + sidx : 1};
+        aes_encrypt(ks4, rk, L);
+        uint32_t y[4] = {0, 0, 0, 0};
+        if (is_data) {
+            uint32_t in4[4], o4[4];
+            const uint4 w = chk.in(src + 16ull * sidx, 16) ? *reinterpret_cast<const uint4 *>(src + 16ull * sidx)
+                                                            : make_uint4(0, 0, 0, 0);  // (skipped: zeros)
+            in4[0] = bswap(w.x), in4[1] = bswap(w.y), in4[2] = bswap(w.z), in4[3] = bswap(w.w);
+#pragma unroll
+            for (int q = 0; q < 4; q++) o4[q] = in4[q] ^ ks4[q];
+            if (chk.out(dst + 16ull * sidx, 16))
+                *reinterpret_cast<uint4 *>(dst + 16ull * sidx) =
+                    make_uint4(bswap(o4[0]), bswap(o4[1]), bswap(o4[2]), bswap(o4[3]));
+#pragma unroll
+            for (int q = 0; q < 4; q++) y[q] = kOpen ? in4[q] : o4[q];
+        } else if (is_len) {  // len(A) = 0 || len(C) in bits
+            y[2] = (uint32_t)(g.clen_bits >> 32);
+            y[3] = (uint32_t)g.clen_bits;
+        } else if (j == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) ekj0[q] = ks4[q];
+        }
+        // Horner step with H^64
+        if (j) {
+            uint32_t m[4];
+            gf_mul8(m, acc, L.h8, L.rem8);
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc[q] = m[q] ^ y[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc[q] = y[q];
+        }
+    }
+    {
+        uint32_t m[4];
+        gf_mul(m, acc, L.htab[63 - lane], L.rem);
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] = m[q];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] ^= __shfl_xor(acc[q], off);
+    if (pad == 0) {  // no padding lane computed AES(K, J0): lane 0 does it now
+        if (lane == 0) {
+            uint32_t k4[4] = {j0w0, j0w1, j0w2, 1};
+            aes_encrypt(k4, rk, L);
+#pragma unroll
+            for (int q = 0; q < 4; q++) ekj0[q] = k4[q];
+        }
+    }
+    if (lane == 0) {
+        uint32_t tag[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) tag[q] = acc[q] ^ ekj0[q];
+        if (kOpen) {
+            const uint8_t *given = src + ib;
+            bool ok = true;
+            if (chk.in(given, 16))
+                for (int i = 0; i < 16; i++) ok &= given[i] == (uint8_t)(tag[i >> 2] >> (24 - 8 * (i & 3)));
+            if (!ok && chk.status(status)) atomicMin(status, (int32_t)b);
+        } else if (chk.out(dst + ib, 16)) {
+            for (int i = 0; i < 16; i++) dst[ib + i] = (uint8_t)(tag[i >> 2] >> (24 - 8 * (i & 3)));
+        }
+    }
+}
+
 #ifndef UPLINK_GCM_WAVES_PER_EU  // (-D for A/B builds: a register budget of 512 / this per lane)
 #define UPLINK_GCM_WAVES_PER_EU 4
 #endif
@@ -351,6 +492,106 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UPLINK_GCM_
     }
 }
 
+// ---- segments of different sizes in one launch (aesgcm.hpp GcmSizedArgs) ----
+
+[[maybe_unused]] constexpr int kSiteGcmIn = 41, kSiteGcmOut = 42, kSiteGcmStatus = 43, kSiteGcmPad = 44;  // (checked build)
+
+// Checked build: a segment's declared extents -- its input, its output and the
+// call's status words.  An access outside is skipped and its site recorded (as
+// blake3.hip in_piece / list_store_ok); in the product build every access passes
+// and the struct is empty.
+struct GcmSizedCheck {
+#ifdef UPLINK_EC_CHECKED
+    const uint8_t *in_lo, *out_lo;
+    uint64_t in_len, out_len;
+    const int32_t *st_lo;
+    uint32_t nseg;
+    uint32_t *flag;
+    __device__ __forceinline__ bool span(const void *p, uint32_t bytes, const uint8_t *lo, uint64_t len, int site) const {
+        const uint8_t *q = static_cast<const uint8_t *>(p);
+        if (q >= lo && (uint64_t)(q - lo) + bytes <= len) return true;
+        if (flag) atomicCAS(flag, 0u, (uint32_t)site);
+        return false;
+    }
+    __device__ __forceinline__ bool in(const void *p, uint32_t bytes) const { return span(p, bytes, in_lo, in_len, kSiteGcmIn); }
+    __device__ __forceinline__ bool out(const void *p, uint32_t bytes) const { return span(p, bytes, out_lo, out_len, kSiteGcmOut); }
+    __device__ __forceinline__ bool status(const void *p) const {
+        return span(p, 4, reinterpret_cast<const uint8_t *>(st_lo), 4ull * nseg, kSiteGcmStatus);
+    }
+#else
+    __device__ __forceinline__ bool in(const void *, uint32_t) const { return true; }
+    __device__ __forceinline__ bool out(const void *, uint32_t) const { return true; }
+    __device__ __forceinline__ bool status(const void *) const { return true; }
+#endif
+};
+
+// A workgroup finds its segment through the pass's map (uniform per workgroup:
+// scalar loads), fills its LDS with that segment's key and runs gcm_blocks' stride
+// loop over the segment's blocks on the segment's own workgroups.
+template <bool kOpen>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UPLINK_GCM_WAVES_PER_EU))) void gcm_blocks_sized(
+    GcmSizedArgs a) {
+    __shared__ Lds L;
+    const GcmSizedDesc *d = a.desc + a.map[blockIdx.x];
+    const uint32_t seg = d->seg, nblocks = d->nblocks, wgs = d->wgs;
+    const uint32_t wg = blockIdx.x - d->wg0;
+    const uint8_t *in = d->in;
+    uint8_t *out = d->out;
+    const GcmSched *ks = a.sched + seg;
+    gcm_fill_lds(L, ks);
+    uint32_t rk[60];
+#pragma unroll
+    for (int i = 0; i < 60; i++) rk[i] = ks->rk[i];  // uniform: scalar loads
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const GcmShape g(a.in_block);
+    uint32_t nw[3];
+    gcm_load_nonce(a.nonces + 12ull * seg, nw);
+    const uint64_t in_blk = kOpen ? (uint64_t)g.ib + 16 : g.ib, out_blk = kOpen ? g.ib : (uint64_t)g.ib + 16;
+    GcmSizedCheck chk;
+#ifdef UPLINK_EC_CHECKED
+    chk = {in, out, in_blk * nblocks, out_blk * nblocks, a.status, a.nseg, a.chk_flag};
+#endif
+
+    for (uint32_t b = wg * 4 + wave; b < nblocks; b += wgs * 4)
+        gcm_block<kOpen>(L, rk, nw, b, in + in_blk * b, out + out_blk * b, g, lane, a.status + seg, chk);
+}
+
+// One workgroup per segment of the pass: its descriptor from the host's staging to
+// device memory, its workgroups' entries of the map, and, for a segment given by its
+// data length, PadReader's padding behind the data (the bytes ec_pad_segments
+// writes).  rs_encode_sized_prep's counterpart (rs_encode_sized.hip).
+__global__ __launch_bounds__(256) void gcm_sized_prep(const GcmSizedStage *stage, GcmSizedDesc *desc, uint32_t *map,
+                                                      uint32_t in_block, uint32_t *chk_flag) {
+    const GcmSizedStage *st = stage + blockIdx.x;
+    const uint32_t tid = threadIdx.x;
+    {
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(&st->d);
+        uint64_t *dst = reinterpret_cast<uint64_t *>(desc + blockIdx.x);
+        for (uint32_t i = tid; i < sizeof(GcmSizedDesc) / 8; i += blockDim.x) dst[i] = src[i];
+    }
+    uint32_t *m = map + st->d.wg0;
+    const uint32_t wgs = st->d.wgs;
+    for (uint32_t i = tid; i < wgs; i += blockDim.x) m[i] = blockIdx.x;
+    // the padding: at most a block and 3 bytes
+    const uint32_t p = st->pad;
+    if (p) {
+        uint8_t *tail = const_cast<uint8_t *>(st->d.in) + st->data_len;
+        for (uint32_t i = tid; i < p; i += blockDim.x) {
+            uint8_t v = (uint8_t)p;
+            if (i + 4 >= p) v = (uint8_t)(p >> (8 * (p - 1 - i)));  // last 4 bytes: big-endian p
+#ifdef UPLINK_EC_CHECKED
+            if (st->data_len + i >= (uint64_t)st->d.nblocks * in_block) {
+                if (chk_flag) atomicCAS(chk_flag, 0u, (uint32_t)kSiteGcmPad);
+                continue;
+            }
+#endif
+            tail[i] = v;
+        }
+    }
+    (void)in_block, (void)chk_flag;
+}
+
 // ---- host helpers ----
 
 uint32_t sub_word(uint32_t w) {
@@ -469,17 +710,37 @@ void gcm_prepare(const uint8_t key[32], GcmSched *out) {
     }
 }
 
+// The grid a launch aims for: 256 CUs times UPLINK_GCM_GRID_PER_CU (1..64, default 32: gcm_launch)
+uint32_t gcm_target_grid() {
+    static const uint32_t per_cu = [] {
+        const char *e = getenv("UPLINK_GCM_GRID_PER_CU");
+        const int v = e ? atoi(e) : 32;
+        return (uint32_t)(v > 0 && v <= 64 ? v : 32);
+    }();
+    return 256 * per_cu;
+}
+
+hipError_t gcm_launch_sized(const GcmSizedPass &p, bool open, hipStream_t stream) {
+    if (p.n == 0 || p.wgs == 0) return hipSuccess;
+    if (p.in_block == 0 || p.in_block > (1u << 24) || p.in_block % 16) return hipErrorInvalidValue;
+    gcm_sized_prep<<<dim3(p.n), 256, 0, stream>>>(p.stage, p.desc, p.map, p.in_block, p.chk_flag);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const GcmSizedArgs a{p.desc, p.map, p.sched, p.nonces, p.status, p.chk_flag, p.in_block, p.nseg};
+    if (open)
+        gcm_blocks_sized<true><<<dim3(p.wgs), 256, 0, stream>>>(a);
+    else
+        gcm_blocks_sized<false><<<dim3(p.wgs), 256, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
 hipError_t gcm_launch(const GcmBatch &b, bool open, hipStream_t stream) {
     if (b.nseg == 0 || b.nblocks == 0) return hipSuccess;
     if (b.in_block == 0 || b.in_block > (1u << 24)) return hipErrorInvalidValue;
     // enough workgroups to fill the chip many times over, each looping over blocks of one segment:
     // 32 per CU (8 segments: seal 167.3 us per segment, against 168.3 at 16, 174.7 at 8, 184.0 at
     // 4; profiles/r05/gcm/ab_grid*.json; UPLINK_GCM_GRID_PER_CU for A/B)
-    static const uint64_t per_cu = [] {
-        const char *e = getenv("UPLINK_GCM_GRID_PER_CU");
-        const int v = e ? atoi(e) : 32;
-        return (uint64_t)(v > 0 && v <= 64 ? v : 32);
-    }();
+    const uint64_t per_cu = gcm_target_grid() / 256;
     uint32_t wgs = (b.nblocks + 3) / 4;
     const uint32_t cap = (uint32_t)((256ull * per_cu + b.nseg - 1) / b.nseg);
     if (wgs > cap) wgs = cap < 1 ? 1 : cap;
@@ -558,6 +819,17 @@ int gcm_run(const uint8_t *in, size_t nseg, size_t nblocks, size_t in_block, con
 }
 
 }  // namespace
+
+hipError_t gcm_status_launch(int32_t *status, uint32_t nseg, bool fini, hipStream_t stream) {
+    if (nseg == 0) return hipSuccess;
+    const unsigned g = (nseg + 255) / 256;
+    if (fini)
+        gcm_status_fini<<<g, 256, 0, stream>>>(status, nseg);
+    else
+        gcm_status_init<<<g, 256, 0, stream>>>(status, nseg);
+    return hipGetLastError();
+}
+
 }  // namespace uplink_ec
 
 using namespace uplink_ec;

@@ -40,6 +40,68 @@ struct GcmBatch {
 
 hipError_t gcm_launch(const GcmBatch &b, bool open, hipStream_t stream);
 
+// The workgroups the uniform launch spreads over a batch (256 * UPLINK_GCM_GRID_PER_CU).
+uint32_t gcm_target_grid();
+
+// status[0..nseg) to "nothing failed yet" before the first launch of an open
+// (fini false), and the words still so to -1 after the last (fini true).
+hipError_t gcm_status_launch(int32_t *status, uint32_t nseg, bool fini, hipStream_t stream);
+
+// ---- segments of different sizes in one launch (include/uplink_ec.h
+// ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized) ----
+//
+// A pass is a list of segments, each of its own number of dense GCM blocks, with
+// its own workgroups (gcm_sized_geom.hpp).  A workgroup finds its segment through
+// a map: one uint32 per workgroup, the position of its segment's descriptor in
+// the pass.  Per pass the host writes a GcmSizedStage per segment into pinned
+// memory; gcm_sized_prep (one workgroup per segment) copies the descriptor to
+// device memory, fills the segment's workgroups' entries of the map and, for a
+// segment given by its data length, writes PadReader's padding behind the data;
+// gcm_blocks_sized then runs the uniform kernel's block body over each segment.
+
+// One segment of a pass, in device memory.
+struct GcmSizedDesc {
+    const uint8_t *in;   // nblocks dense blocks: in_block bytes each to seal, in_block + 16 to open
+    uint8_t *out;        // nblocks dense blocks: in_block + 16 bytes each sealed, in_block opened
+    uint32_t nblocks;
+    uint32_t wg0, wgs;   // its first workgroup in the pass's grid and how many it has
+    uint32_t seg;        // its index in the call: key, nonce and status word
+};
+static_assert(sizeof(GcmSizedDesc) == 32, "copied as 8-byte words");
+
+// What the host writes per segment (pinned memory, read once by gcm_sized_prep).
+struct GcmSizedStage {
+    GcmSizedDesc d;
+    uint64_t data_len;  // with pad > 0: the padding goes to in[data_len ..]
+    uint32_t pad;       // PadReader's byte count p (0: the segment is already padded)
+    uint32_t rsv;
+};
+
+// Kernel arguments of gcm_blocks_sized.
+struct GcmSizedArgs {
+    const GcmSizedDesc *desc;  // the pass's descriptors
+    const uint32_t *map;       // [workgroup] -> position of its segment's descriptor
+    const GcmSched *sched;     // [nseg] of the call
+    const uint8_t *nonces;     // [nseg][12] of the call
+    int32_t *status;           // [nseg] of the call (open)
+    uint32_t *chk_flag;        // checked build: first access outside a segment's extents (sites 41-44)
+    uint32_t in_block, nseg;
+};
+
+// One pass: the prep launch, then the cipher, on `stream`.
+struct GcmSizedPass {
+    const GcmSizedStage *stage;  // [n] pinned, device-visible
+    GcmSizedDesc *desc;          // [n] device
+    uint32_t *map;               // [wgs] device
+    uint32_t n, wgs;
+    const GcmSched *sched;
+    const uint8_t *nonces;
+    int32_t *status;
+    uint32_t nseg, in_block;
+    uint32_t *chk_flag;
+};
+hipError_t gcm_launch_sized(const GcmSizedPass &p, bool open, hipStream_t stream);
+
 // AES-256 of one block on the host (key setup and tests)
 void aes256_encrypt_block(const uint32_t rk[60], const uint8_t in[16], uint8_t out[16]);
 

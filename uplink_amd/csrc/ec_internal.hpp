@@ -498,6 +498,9 @@ struct ec_ctx {
     // launches of those two calls so far: fast chunk launches, byte chunk launches, parents
     // launches, oversize pieces sent through the uniform launch (ec_hash_list_stats)
     std::atomic<uint64_t> hl_fast{0}, hl_byte{0}, hl_parents{0}, hl_oversize{0};
+    RepairPool gcm_sized;  // staging of ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized (ec_gcm_sized.cpp)
+    // cipher launches of those two calls so far, and their passes (ec_gcm_sized_stats)
+    std::atomic<uint64_t> gs_seal{0}, gs_open{0}, gs_passes{0};
     SlBuilder slb;
 };
 

@@ -10,6 +10,8 @@ are objects.  Here they are one stream-ordered pass on the GPU.
 
   segment_geometry   (padded_size, piece_size, nstripes) of a download
   decode_downloads   the plaintext-sized outputs of a batch of downloads
+  open_downloads     the decrypted plaintexts of a batch of decoded downloads
+                     (ec_gcm_open_segments_sized)
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ from typing import Dict, List, Sequence, Tuple
 from . import _native as N
 from .ecclient import calc_padded
 from .eestream import SegmentCodec, _raise
+from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, DecryptionFailed, open_segments_sized
 
 
 def segment_geometry(size: int, es) -> Tuple[int, int, int]:
@@ -85,6 +88,52 @@ def decode_downloads(scheme, downloads: Sequence[Tuple[int, Dict[int, object]]],
             codec.rebuild_segments_sized(sets, nstripes, ptrs, stream=stream)
     res = [o[:size] for o, (size, _) in zip(outs, geo)]
     return (res, errors) if collect_errors else res
+
+
+def open_downloads(scheme, sealed: Sequence[Tuple[int, object]], dev_keys, dev_nonces, *,
+                   block_size: int = DEFAULT_BLOCK_SIZE, check: bool = False, stream=None):
+    """decryptRanger (streams/store.go:347-382) over a batch: sealed is per
+    download (plain_size, enc), `enc` the uint8 device tensor of exactly the
+    enc_len bytes (uploads.cipher_geometry) of its encrypted segment, as
+    decode_downloads returns it; another length raises ValueError.  Download g
+    is opened under prepared key g of dev_keys and nonce
+    dev_nonces[12*g:12*g+12].  Returns (plains, status): plains[g] is a device
+    tensor of exactly plain_size bytes (the padding cut off, as store.go:381)
+    and status the [nseg] int32 device tensor, -1 or the first block of
+    download g whose tag did not verify (its plaintext is not to be used).
+    Asynchronous on `stream`; with check=True it waits and raises
+    DecryptionFailed(block) for the first failing download."""
+    import torch
+
+    from .uploads import cipher_geometry
+
+    geo = []
+    dev = None
+    for size, enc in sealed:
+        nblocks, plain_cap, enc_len = cipher_geometry(int(size), block_size)
+        if enc.dtype != torch.uint8 or not enc.is_contiguous():
+            raise ValueError("a download's encrypted segment is a contiguous uint8 tensor")
+        if enc.numel() != enc_len:
+            raise ValueError(f"a download of {int(size)} bytes has {enc_len} encrypted bytes, got {enc.numel()}")
+        if dev is None:
+            dev = enc.device
+        geo.append((int(size), nblocks, plain_cap, enc))
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        outs = [torch.empty(g[2], dtype=torch.uint8, device=dev) for g in geo]
+        status = torch.empty(len(geo), dtype=torch.int32, device=dev)
+        if geo:
+            open_segments_sized(scheme, [g[3] for g in geo], [g[1] for g in geo], block_size - TAG_SIZE, dev_keys,
+                                dev_nonces, outs, status, stream=stream)
+        if check:
+            if stream is not None and ts is None:  # a raw stream handle: not the stream the copy below runs on
+                torch.cuda.synchronize()
+            for block in status.cpu().tolist():  # (a copy on the current stream: it waits for the open)
+                if block >= 0:
+                    raise DecryptionFailed(block)
+    return [o[:g[0]] for o, g in zip(outs, geo)], status
 
 
 class _Null:

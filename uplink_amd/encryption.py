@@ -154,6 +154,53 @@ def seal_segments(plain, nseg: int, nblocks: int, in_block: int, dev_keys, dev_n
     _raise(None, rc)
 
 
+def _sized_lists(what, bufs, nblocks, outs):
+    nblocks = [int(x) for x in nblocks]
+    bufs, outs = list(bufs), list(outs)
+    if len(bufs) != len(nblocks) or len(outs) != len(nblocks):
+        raise ValueError(f"one {what}, one block count and one output per segment")
+    if any(x < 0 for x in nblocks):
+        raise ValueError("a block count is negative")
+    from .eestream import SegmentCodec as C
+    n = max(len(nblocks), 1)
+    c_in = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in bufs])
+    c_out = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in outs])
+    return len(nblocks), c_in, (ctypes.c_size_t * n)(*nblocks), c_out
+
+
+def seal_segments_sized(scheme, plains, nblocks, in_block: int, dev_keys, dev_nonces, outs, data_len=None,
+                        stream=None):
+    """seal_segments with a block count, key and nonce per segment
+    (ec_gcm_seal_segments_sized): plains[g] is nblocks[g]*in_block bytes,
+    outs[g] nblocks[g]*(in_block+16); entries are tensors, addresses or None
+    (a segment of 0 blocks).  With data_len, segment g holds data_len[g] bytes
+    and PadReader's padding to in_block is written behind them before the seal.
+    `scheme` supplies the device and the staging.  Asynchronous on `stream`."""
+    from .eestream import SegmentCodec as C
+    nseg, c_in, c_nb, c_out = _sized_lists("plaintext", plains, nblocks, outs)
+    c_len = None
+    if data_len is not None:
+        data_len = [int(x) for x in data_len]
+        if len(data_len) != nseg or any(x < 0 for x in data_len):
+            raise ValueError("one non-negative data length per segment")
+        c_len = (ctypes.c_size_t * max(nseg, 1))(*data_len)
+    rc = N.load().ec_gcm_seal_segments_sized(scheme.ctx, nseg, c_in, c_nb, c_len, int(in_block), C._addr(dev_keys),
+                                             C._addr(dev_nonces), c_out, C._stream(stream))
+    _raise(scheme.ctx, rc)
+
+
+def open_segments_sized(scheme, ciphers, nblocks, in_block: int, dev_keys, dev_nonces, outs, dev_status,
+                        stream=None):
+    """ec_gcm_open_segments_sized: ciphers[g] is nblocks[g]*(in_block+16) bytes,
+    outs[g] nblocks[g]*in_block; dev_status is [nseg] int32 on the device and
+    dev_status[g] ends as -1 or the first failing block of segment g."""
+    from .eestream import SegmentCodec as C
+    nseg, c_in, c_nb, c_out = _sized_lists("ciphertext", ciphers, nblocks, outs)
+    rc = N.load().ec_gcm_open_segments_sized(scheme.ctx, nseg, c_in, c_nb, int(in_block), C._addr(dev_keys),
+                                             C._addr(dev_nonces), c_out, C._addr(dev_status), C._stream(stream))
+    _raise(scheme.ctx, rc)
+
+
 def open_segments(cipher, nseg: int, nblocks: int, in_block: int, dev_keys, dev_nonces, out, dev_status,
                   stream=None):
     """ec_gcm_open_segments; dev_status[g] = -1 or the first failing block."""
