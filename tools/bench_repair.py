@@ -48,9 +48,10 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the byte sums of every regenerated piece of the last direct launch per target count "
                          "as DIR/repair_bytesum_m<targets>.npy (float64 [nseg][targets])")
+    ap.add_argument("--lib", default=_native.LIB_PATH, help="another build of libuplink_ec.so (A/B runs of library variants)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
-    L = _native.load()
+    L = _native.load(args.lib)
     ctx = ctypes.c_void_p()
     assert L.ec_create(K, N, ESS, ctypes.byref(ctx)) == 0
     dev = torch.device("cuda", 0)

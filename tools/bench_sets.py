@@ -38,9 +38,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=24)
     ap.add_argument("--nseg", type=int, default=32)
+    ap.add_argument("--lib", default=_native.LIB_PATH, help="another build of libuplink_ec.so (A/B runs of library variants)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
-    L = _native.load()
+    L = _native.load(args.lib)
     ctx = ctypes.c_void_p()
     assert L.ec_create(K, N, ESS, ctypes.byref(ctx)) == 0
     dev = torch.device("cuda", 0)

@@ -43,9 +43,10 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0, help="device time per arm and workload, at least")
     ap.add_argument("--rounds", type=int, default=5, help="alternations of the two arms per workload, at least")
     ap.add_argument("--workloads", nargs="*", default=["small", "mixed", "equal"])
+    ap.add_argument("--lib", default=_native.LIB_PATH, help="another build of libuplink_ec.so (A/B runs of library variants)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
-    L = _native.load()
+    L = _native.load(args.lib)
     ctx = ctypes.c_void_p()
     assert L.ec_create(K, N, ESS, ctypes.byref(ctx)) == 0
     dev = torch.device("cuda", 0)

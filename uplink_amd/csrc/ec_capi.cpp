@@ -844,14 +844,6 @@ static int pipe_drain(ec_ctx *c, int rc) {
     return rc;
 }
 
-}  // extern "C"
-namespace uplink_ec {
-namespace capi {
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-}  // namespace capi
-}  // namespace uplink_ec
-extern "C" {
-
 // ---------------------------------------------------------------- per-stripe
 // single_batch_once: one launch sequence for the whole batch, or kSplit when
 // the staging for it cannot be had (and the batch has more than one request)
@@ -883,8 +875,8 @@ static int single_batch_once(ec_ctx *c, SingleReq *const *req, size_t nreq, size
     const size_t stripe = (size_t)k * bs;
     const size_t in_bytes = nreq * stripe, par_bytes = (size_t)(n - k) * nreq * bs, out_bytes = nreq * bs;
     // device: [stripes | nums | parity | out]; pinned host: [stripes | nums | out]
-    const size_t nums_at = align_up(in_bytes, 256), par_at = nums_at + align_up(nreq * 4, 256);
-    const size_t out_at = par_at + align_up(par_bytes, 256), h_out = par_at;
+    const size_t nums_at = up(in_bytes, 256), par_at = nums_at + up(nreq * 4, 256);
+    const size_t out_at = par_at + up(par_bytes, 256), h_out = par_at;
     if (c->fault_max_batch > 0 &&
         (nreq > (size_t)c->fault_max_batch || (nreq == 1 && req[0]->num == c->fault_fail_num)))
         return nreq == 1 ? EC_ERR_DEVICE : kSplit;  // (test hook, see ec_ctx)
@@ -1157,13 +1149,13 @@ B3View parity_view(const ec_ctx *c, const uint8_t *parity, size_t nseg, size_t n
 size_t b3_segment_ws_bytes(const ec_ctx *c, size_t nseg, size_t nstripes) {
     B3View all = parity_view(c, nullptr, nseg, nstripes);
     all.npieces = nseg * (uint64_t)c->n;
-    return align_up(b3_workspace_bytes(all), 256) + align_up(32 * nseg * (size_t)c->n, 256);
+    return up(b3_workspace_bytes(all), 256) + up(32 * nseg * (size_t)c->n, 256);
 }
 int hash_segments(const ec_ctx *c, const uint8_t *segs, const uint8_t *parity, size_t nseg, size_t nstripes,
                          uint8_t *hashes, uint8_t *ws, hipStream_t st) {
     const size_t n = c->n, k = c->k;
     uint8_t *stage = ws;  // [data: nseg*k*32][parity: nseg*(n-k)*32]
-    uint8_t *tree = ws + align_up(32 * nseg * n, 256);
+    uint8_t *tree = ws + up(32 * nseg * n, 256);
     B3View pv = parity_view(c, parity, nseg, nstripes);
     if (n == k) pv.npieces = 0;
     HIP_TRY(b3_launch2(data_view(c, segs, nseg, nstripes), pv, stage, tree, st));
@@ -1194,7 +1186,7 @@ static int encode_host(ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstri
     const int rows = parity_only ? c->n - c->k : c->n;
     const size_t plen = nstripes * ess, pbytes = (size_t)rows * plen;
     // device slot: pieces | hashes (n*32) | BLAKE3 workspace
-    const size_t hash_at = align_up(pbytes, 256), ws_at = hash_at + align_up(32 * (size_t)c->n, 256);
+    const size_t hash_at = up(pbytes, 256), ws_at = hash_at + up(32 * (size_t)c->n, 256);
     const size_t out_cap = hashes ? ws_at + b3_segment_ws_bytes(c, 1, nstripes) : std::max<size_t>(pbytes, 1);
     const size_t nch = std::min<size_t>(8, std::max<size_t>(1, nstripes / 256));
     const size_t chunk = (nstripes + nch - 1) / nch;
@@ -1297,8 +1289,8 @@ int ec_blake3_host(const uint8_t *data, size_t npieces, long long stride, size_t
     int rc = EC_OK;
     do {
         if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { rc = EC_ERR_DEVICE; break; }
-        if (hipMalloc(&d, align_up(span, 256) + 32 * npieces) != hipSuccess) { rc = EC_ERR_DEVICE; d = nullptr; break; }
-        uint8_t *dh = d + align_up(span, 256);
+        if (hipMalloc(&d, up(span, 256) + 32 * npieces) != hipSuccess) { rc = EC_ERR_DEVICE; d = nullptr; break; }
+        uint8_t *dh = d + up(span, 256);
         if (span && hipMemcpyAsync(d, data, span, hipMemcpyHostToDevice, st) != hipSuccess) { rc = EC_ERR_DEVICE; break; }
         rc = ec_blake3_pieces(d, npieces, stride, piece_len, piece_len, stride, dh, st);
         if (rc) break;

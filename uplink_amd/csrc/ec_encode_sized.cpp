@@ -13,71 +13,6 @@ namespace uplink_ec {
 namespace capi {
 namespace {
 
-size_t pow2_at_least(size_t n, size_t lo) {
-    size_t c = lo;
-    while (c < n) c *= 2;
-    return c;
-}
-
-size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-}  // namespace
-
-// A block of the context's pool with room for h_need pinned and d_need device
-// bytes whose previous pass has finished on the GPU, or a new one (sized in
-// powers of two).  nullptr: no memory.  (RepairBlock's mechanism, ec_repair.cpp;
-// the limit on blocks in flight counts the blocks large enough for this pass, so
-// that a pool full of small blocks from small batches does not make a call with
-// a larger pass wait for the few blocks that fit it.)
-RepairBlock *block_acquire(RepairPool &P, size_t h_need, size_t d_need) {
-    RepairBlock *b = nullptr, *oldest = nullptr;
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        size_t fit = 0;
-        for (auto &x : P.blocks) {
-            if (x->h_cap < h_need || x->d_cap < d_need) continue;
-            fit++;
-            if (x->busy) continue;
-            if (!oldest) oldest = x.get();
-            if (x->idle()) {
-                b = x.get();
-                break;
-            }
-        }
-        if (!b && fit >= RepairPool::kMaxBlocks) b = oldest;  // waited for below
-        if (!b) {
-            auto x = std::make_unique<RepairBlock>();
-            x->h_cap = pow2_at_least(h_need, 64u << 10);
-            x->d_cap = pow2_at_least(d_need, 256u << 10);
-            if (hipHostMalloc((void **)&x->h, x->h_cap, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-                hipMalloc((void **)&x->d, x->d_cap) != hipSuccess ||
-                hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess)
-                return nullptr;  // (its destructor frees what it got)
-            P.blocks.push_back(std::move(x));
-            b = P.blocks.back().get();
-        }
-        b->busy = true;
-    }
-    if (b->queued && hipEventSynchronize(b->ev) != hipSuccess) {
-        std::lock_guard<std::mutex> g(P.mu);
-        b->busy = false;
-        return nullptr;
-    }
-    b->queued = false;
-    return b;
-}
-
-// Hand the block back; `launched`: something that reads it was queued on s.
-void block_release(RepairPool &P, RepairBlock *b, bool launched, hipStream_t s) {
-    // (an event that cannot be recorded leaves the block to a wait for the stream)
-    if (launched && hipEventRecord(b->ev, s) != hipSuccess) (void)hipStreamSynchronize(s);
-    std::lock_guard<std::mutex> g(P.mu);
-    b->queued = launched;
-    b->busy = false;
-}
-
-namespace {
-
 // One segment the sized kernel takes.
 struct EncSeg {
     const uint8_t *in;
@@ -94,7 +29,7 @@ int encode_sized_pass(ec_ctx *c, const EncoderKernel &ek, const EncSeg *segs, si
     for (size_t i = 0; i < n; i++) blocks[i] = segs[i].blocks;
     const int64_t B = sized::first_blocks(blocks.data(), n, block0.data());
     const size_t d_desc = up(n * sizeof(EncSizedDesc), 256), d_map = up((size_t)B * 4, 256);
-    RepairBlock *b = block_acquire(c->enc_sized, n * sizeof(EncSizedStage), d_desc + d_map);
+    StageBlock *b = block_acquire(c->enc_sized, n * sizeof(EncSizedStage), d_desc + d_map);
     if (!b) return EC_ERR_DEVICE;
     EncSizedStage *stage = (EncSizedStage *)b->h;
     EncSizedDesc *d_descs = (EncSizedDesc *)b->d;
@@ -173,8 +108,7 @@ int ec_encode_segments_sized(const ec_ctx *cc, size_t nseg, uint8_t *const *segs
     }
     if (fast.empty() && own.empty()) return EC_OK;
     // staging blocks are recycled by events behind launches that run: not under stream capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
     // another (k, n), n == k, a share size that is no multiple of 16, a misaligned pointer:
     // such a segment on its own, padded and encoded with its own stripe count
     for (size_t g : own) {

@@ -15,8 +15,6 @@ namespace uplink_ec {
 namespace capi {
 namespace {
 
-size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 // One segment the sized kernel takes (skipped segments are not listed).
 struct GcmSeg {
     const uint8_t *in;
@@ -33,8 +31,8 @@ int gcm_sized_pass(ec_ctx *c, const GcmSeg *segs, size_t n, size_t nseg, size_t 
     for (size_t i = 0; i < n; i++) nb[i] = segs[i].nblocks;
     const gcmsized::Layout L = gcmsized::layout(nb.data(), n, gcm_target_grid());
     if (L.map.empty()) return EC_OK;
-    const size_t d_desc = up256(n * sizeof(GcmSizedDesc));
-    RepairBlock *b = block_acquire(c->gcm_sized, n * sizeof(GcmSizedStage), d_desc + up256(L.map.size() * 4));
+    const size_t d_desc = up(n * sizeof(GcmSizedDesc), 256);
+    StageBlock *b = block_acquire(c->gcm_sized, n * sizeof(GcmSizedStage), d_desc + up(L.map.size() * 4, 256));
     if (!b) return EC_ERR_DEVICE;
     GcmSizedStage *stage = (GcmSizedStage *)b->h;
     for (size_t i = 0; i < n; i++) {
@@ -94,8 +92,7 @@ int gcm_sized(const ec_ctx *cc, size_t nseg, const uint8_t *const *in, const siz
     }
     DeviceGuard dg(c->device);
     // staging blocks are recycled by events behind launches that run: not under stream capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
     // the status words: set once before the first pass, finished once after the last
     if (open) HIP_TRY(gcm_status_launch(status, (uint32_t)nseg, false, s));
     for (const sized::Pass &p : gcmsized::split(list.size()))

@@ -13,8 +13,6 @@ namespace uplink_ec {
 namespace capi {
 namespace {
 
-size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 // One piece to hash and where its 32 bytes go.
 struct HashPiece {
     b3list::Piece p;
@@ -29,10 +27,10 @@ int hash_list_pass(ec_ctx *c, const HashPiece *pieces, const b3list::Class *cls,
     for (size_t i = 0; i < n; i++) ps[i] = pieces[i].p;
     const b3list::Layout L = b3list::layout(ps.data(), cls, n);
     if (L.wgs[0] + L.wgs[1] == 0) return EC_OK;  // (oversize pieces only)
-    const size_t desc_bytes = up256(n * sizeof(B3ListDesc)), map_bytes = up256(L.map.size() * 4),
-                 par_bytes = up256(L.parents.size() * 4);
+    const size_t desc_bytes = up(n * sizeof(B3ListDesc), 256), map_bytes = up(L.map.size() * 4, 256),
+                 par_bytes = up(L.parents.size() * 4, 256);
     const size_t stage_bytes = desc_bytes + map_bytes + par_bytes;
-    RepairBlock *b = block_acquire(c->hash_sized, stage_bytes, stage_bytes + (size_t)L.nodes * 32);
+    StageBlock *b = block_acquire(c->hash_sized, stage_bytes, stage_bytes + (size_t)L.nodes * 32);
     if (!b) return EC_ERR_DEVICE;
     B3ListDesc *hd = (B3ListDesc *)b->h;
     for (size_t i = 0; i < n; i++) {
@@ -93,8 +91,7 @@ int hash_oversize(ec_ctx *c, const HashPiece &hp, hipStream_t s) {
 int hash_list(ec_ctx *c, const std::vector<HashPiece> &pieces, uint8_t *hash_lo, uint8_t *hash_hi, hipStream_t s) {
     if (pieces.empty()) return EC_OK;
     // staging blocks are recycled by events behind launches that run: not under stream capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
     std::vector<b3list::Piece> ps(pieces.size());
     std::vector<b3list::Class> cls(pieces.size());
     for (size_t i = 0; i < pieces.size(); i++) {

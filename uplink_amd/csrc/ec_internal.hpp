@@ -334,22 +334,24 @@ struct SetsRing {
     std::vector<std::unique_ptr<SetsSlot>> slots;
 };
 
-// Staging of one repair call (ec_repair_segments_sets, rs_repair.hpp): the
-// pinned memory the host writes its segments' records and coefficients into and
-// the device memory rs_repair_prep makes descriptors and leaf tables in.  An
-// event recorded behind the call's last launch tells when both are free again:
-// a block is taken under the pool's mutex, reused once its event has completed
-// (hipEventQuery, no wait), and another is made when none is free, so a call
-// waits for nothing queued earlier.  Blocks are sized in powers of two and kept
-// until ec_destroy (a free on the call path would synchronise the device).
-struct RepairBlock {
+// Staging of one pass of a call that prepares its segments on the host (segment
+// repair and the *_sized calls; first ec_repair_segments_sets, rs_repair.hpp):
+// the pinned memory the host writes its segments' records and coefficients into
+// and the device memory the pass's prep kernel makes descriptors, leaf tables
+// and maps in.  An event recorded behind the pass's last launch tells when both
+// are free again: a block is taken under the pool's mutex, reused once its
+// event has completed (hipEventQuery, no wait), and another is made when none
+// is free, so a call waits for nothing queued earlier (ec_stage.cpp).  Blocks
+// are sized in powers of two and kept until ec_destroy (a free on the call path
+// would synchronise the device).
+struct StageBlock {
     uint8_t *h = nullptr, *d = nullptr;
     size_t h_cap = 0, d_cap = 0;
     hipEvent_t ev = nullptr;
     bool busy = false;    // a caller is filling or launching it
     bool queued = false;  // ev is recorded behind launches that read the block
     bool idle() const { return !busy && (!queued || hipEventQuery(ev) == hipSuccess); }
-    ~RepairBlock() {
+    ~StageBlock() {
         if (queued && ev) (void)hipEventSynchronize(ev);
         if (ev) (void)hipEventDestroy(ev);
         if (h) (void)hipHostFree(h);
@@ -357,40 +359,14 @@ struct RepairBlock {
     }
 };
 
-struct RepairPool {
+struct StagePool {
     // blocks in flight per context before a caller waits for the oldest (a
     // caller that queues without end must not take pinned memory without end)
     static constexpr size_t kMaxBlocks = 256;
+    const size_t d_min;  // device bytes of a new block at least
     std::mutex mu;
-    std::vector<std::unique_ptr<RepairBlock>> blocks;
-};
-
-// Lagrange interpolation through the points of k basis shares (piece numbers
-// ids[0..k)), in logarithms: the closed form of rs_sets.hip (solve_rows).
-// row(y, out): out[p] = L_p(y), the coefficient of basis share p in the share
-// at point y -- a unit vector when y is itself a basis point.
-struct LagrangeBasis {
-    int k = 0;
-    uint8_t x[kMaxOps];
-    int lw[kMaxOps];  // log W_p, W_p = prod over t != p of (x_p - x_t)
-    LagrangeBasis(const int *ids, int k_) : k(k_) {
-        for (int p = 0; p < k; p++) x[p] = gf_point(ids[p]);
-        for (int p = 0; p < k; p++) {
-            int l = 0;
-            for (int t = 0; t < k; t++)
-                if (t != p) l += kGf.log[x[p] ^ x[t]];
-            lw[p] = l % 255;
-        }
-    }
-    void row(uint8_t y, uint8_t *out) const {
-        int ln = 0, hit = -1;
-        for (int t = 0; t < k; t++) {
-            if (y == x[t]) hit = t;
-            else ln += kGf.log[y ^ x[t]];
-        }
-        for (int j = 0; j < k; j++)
-            out[j] = hit >= 0 ? (uint8_t)(hit == j) : kGf.exp[(((ln - kGf.log[y ^ x[j]] - lw[j]) % 255) + 255) % 255];
-    }
+    std::vector<std::unique_ptr<StageBlock>> blocks;
+    explicit StagePool(size_t d_min_) : d_min(d_min_) {}
 };
 
 // Background maker of decode plans' straight-line code (DESIGN.md §4
@@ -487,18 +463,18 @@ struct ec_ctx {
     // UPLINK_EC_SETS_ONE=0 at ec_create for the two launches (A/B)
     bool sets_one = true;
     SetsRing sets;
-    RepairPool repair;  // staging of ec_repair_segments_sets
-    RepairPool sized;   // staging of ec_*_segments_sized (ec_sized.cpp): the same mechanism, a pool of its own
+    StagePool repair{512u << 10};  // staging of ec_repair_segments_sets
+    StagePool sized{512u << 10};   // staging of ec_*_segments_sized (ec_sized.cpp): the same mechanism, a pool of its own
     // the sized calls launch per wave-count class; UPLINK_EC_SIZED_MERGE=1 at ec_create puts every
     // segment of a pass on the widest class's workgroups instead (one launch, one tail, as
     // sets_merge does for the share-set calls): the A/B of DESIGN.md §4h
     bool sized_merge = false;
-    RepairPool enc_sized;  // staging of ec_encode_segments_sized (ec_encode_sized.cpp): a pool of its own
-    RepairPool hash_sized;  // staging of ec_blake3_pieces_list / ec_hash_segments_sized (ec_hash_sized.cpp)
+    StagePool enc_sized{256u << 10};  // staging of ec_encode_segments_sized (ec_encode_sized.cpp): a pool of its own
+    StagePool hash_sized{256u << 10};  // staging of ec_blake3_pieces_list / ec_hash_segments_sized (ec_hash_sized.cpp)
     // launches of those two calls so far: fast chunk launches, byte chunk launches, parents
     // launches, oversize pieces sent through the uniform launch (ec_hash_list_stats)
     std::atomic<uint64_t> hl_fast{0}, hl_byte{0}, hl_parents{0}, hl_oversize{0};
-    RepairPool gcm_sized;  // staging of ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized (ec_gcm_sized.cpp)
+    StagePool gcm_sized{256u << 10};  // staging of ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized (ec_gcm_sized.cpp)
     // cipher launches of those two calls so far, and their passes (ec_gcm_sized_stats)
     std::atomic<uint64_t> gs_seal{0}, gs_open{0}, gs_passes{0};
     SlBuilder slb;
@@ -548,18 +524,28 @@ void queue_done(ec_ctx *c, hipStream_t s, int slot, uint32_t seq, bool launched)
 // no_jit: never start a run-time compile of this code's encoder (ec_encode_segments_sized)
 int encode_range(ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstripes, size_t s0, size_t s1,
                  uint8_t *pieces, int flags, hipStream_t s, bool shape_probe = false, bool no_jit = false);
-size_t align_up(size_t x, size_t a);
 B3View data_view(const ec_ctx *c, const uint8_t *segs, size_t nseg, size_t nstripes);
 B3View parity_view(const ec_ctx *c, const uint8_t *parity, size_t nseg, size_t nstripes);
 size_t b3_segment_ws_bytes(const ec_ctx *c, size_t nseg, size_t nstripes);
 int hash_segments(const ec_ctx *c, const uint8_t *segs, const uint8_t *parity, size_t nseg, size_t nstripes,
                   uint8_t *hashes, uint8_t *ws, hipStream_t st);
 
-// ec_encode_sized.cpp: a block of pool P with room for h_need pinned and d_need device bytes
+// ec_stage.cpp: a block of pool P with room for h_need pinned and d_need device bytes
 // whose previous pass has finished on the GPU, or a new one (nullptr: no memory); and its
 // return, `launched` when something that reads it was queued on s
-RepairBlock *block_acquire(RepairPool &P, size_t h_need, size_t d_need);
-void block_release(RepairPool &P, RepairBlock *b, bool launched, hipStream_t s);
+StageBlock *block_acquire(StagePool &P, size_t h_need, size_t d_need);
+void block_release(StagePool &P, StageBlock *b, bool launched, hipStream_t s);
+// Staging recycled by events or completion words behind launches needs those launches to run:
+// such calls answer EC_ERR_UNSUPPORTED on a stream that is capturing (or cannot say).
+bool stream_is_capturing(hipStream_t s);
+
+inline size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// the smallest lo * 2^i that is at least n
+inline size_t pow2_at_least(size_t n, size_t lo) {
+    size_t c = lo;
+    while (c < n) c *= 2;
+    return c;
+}
 
 // ec_sets.cpp
 void stop_builder(ec_ctx *c);  // stop and join the context's straight-line builder (ec_destroy)

@@ -20,73 +20,6 @@ struct RepairSeg {
     bool bits = true;
 };
 
-// Row r of the segment's matrix (nin columns): target r from the basis, then
-// one syndrome row per non-basis input (its prediction from the basis, and 1 on
-// the input itself: the two cancel when the share agrees).
-void solve_rows(const RepairSeg &sg, int k, std::vector<uint8_t> &M) {
-    const int nin = (int)sg.in.size(), nt = (int)sg.tnum.size();
-    const LagrangeBasis L(sg.num.data(), k);
-    M.assign((size_t)sg.rows * nin, 0);
-    for (int r = 0; r < sg.rows; r++) {
-        L.row(gf_point(r < nt ? sg.tnum[r] : sg.num[k + r - nt]), &M[(size_t)r * nin]);
-        if (r >= nt) M[(size_t)r * nin + k + r - nt] = 1;
-    }
-}
-
-size_t pow2_at_least(size_t n, size_t lo) {
-    size_t c = lo;
-    while (c < n) c *= 2;
-    return c;
-}
-
-// A block with room for h_need pinned and d_need device bytes whose previous
-// call has finished on the GPU, or a new one.  nullptr: no memory.
-RepairBlock *repair_acquire(ec_ctx *c, size_t h_need, size_t d_need) {
-    RepairPool &P = c->repair;
-    RepairBlock *b = nullptr, *oldest = nullptr;
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        for (auto &x : P.blocks) {
-            if (x->busy) continue;
-            if (x->h_cap < h_need || x->d_cap < d_need) continue;
-            if (!oldest) oldest = x.get();  // (blocks are reused in the order they were made)
-            if (x->idle()) {
-                b = x.get();
-                break;
-            }
-        }
-        if (!b && P.blocks.size() >= RepairPool::kMaxBlocks) b = oldest;  // waited for below
-        if (!b) {
-            auto x = std::make_unique<RepairBlock>();
-            x->h_cap = pow2_at_least(h_need, 64u << 10);
-            x->d_cap = pow2_at_least(d_need, 512u << 10);
-            if (hipHostMalloc((void **)&x->h, x->h_cap, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-                hipMalloc((void **)&x->d, x->d_cap) != hipSuccess ||
-                hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess)
-                return nullptr;  // (its destructor frees what it got)
-            P.blocks.push_back(std::move(x));
-            b = P.blocks.back().get();
-        }
-        b->busy = true;
-    }
-    if (b->queued && hipEventSynchronize(b->ev) != hipSuccess) {
-        std::lock_guard<std::mutex> g(P.mu);
-        b->busy = false;
-        return nullptr;
-    }
-    b->queued = false;
-    return b;
-}
-
-// Hand the block back; `launched`: something that reads it was queued on s.
-void repair_release(ec_ctx *c, RepairBlock *b, bool launched, hipStream_t s) {
-    // (an event that cannot be recorded leaves the block to a wait for the stream)
-    if (launched && hipEventRecord(b->ev, s) != hipSuccess) (void)hipStreamSynchronize(s);
-    std::lock_guard<std::mutex> g(c->repair.mu);
-    b->queued = launched;
-    b->busy = false;
-}
-
 // A segment the bit-sliced kernel cannot take, through the plan path: the
 // matrix from the host under a key of its own kind, the byte kernel with
 // piece -> piece geometry (both strides ess, so a column's offset is the same
@@ -156,10 +89,10 @@ int repair_call(ec_ctx *c, std::vector<RepairSeg> &segs, int64_t nstripes, int32
     std::vector<size_t> eoff(nb + 1, 0);
     for (size_t q = 0; q < nb; q++) {
         const RepairSeg &sg = segs[idx[q]];
-        eoff[q + 1] = eoff[q] + repair_tgt_entries((int)sg.in.size(), sg.rows, sg.nw);
+        eoff[q + 1] = eoff[q] + staged_entries((int)sg.in.size(), sg.rows, sg.nw);
     }
-    const size_t h_stage = nb * sizeof(RepairStage), d_desc = (nb * sizeof(RepairDesc) + 255) & ~(size_t)255;
-    RepairBlock *b = repair_acquire(c, h_stage + eoff[nb], d_desc + eoff[nb] * 8);
+    const size_t h_stage = nb * sizeof(RepairStage), d_desc = up(nb * sizeof(RepairDesc), 256);
+    StageBlock *b = block_acquire(c->repair, h_stage + eoff[nb], d_desc + eoff[nb] * 8);
     if (!b) return EC_ERR_DEVICE;
     RepairStage *stage = (RepairStage *)b->h;
     uint8_t *h_coef = b->h + h_stage;
@@ -181,24 +114,14 @@ int repair_call(ec_ctx *c, std::vector<RepairSeg> &segs, int64_t nstripes, int32
         st.d.nw = nw;
         st.coef = h_coef + eoff[q];
         st.entries = (int64_t)(eoff[q + 1] - eoff[q]);
-        // the coefficients in the leaf table's order: [pass][input][group][8], a group's rows right-aligned
-        solve_rows(sg, k, M);
-        uint8_t *cf = h_coef + eoff[q];
-        memset(cf, 0, (size_t)st.entries);
-        const int npass = repair_npass(sg.rows, nw);
-        for (int pass = 0; pass < npass; pass++)
-            for (int g = 0; g < nw; g++) {
-                int rb, cn;
-                repair_rows_of(pass, npass, sg.rows, nw, g, rb, cn);
-                for (int j = 0; j < nin; j++) {
-                    uint8_t *e = cf + (((size_t)pass * nin + j) * nw + g) * 8 + (8 - cn);
-                    for (int o = 0; o < cn; o++) e[o] = M[(size_t)(rb + o) * nin + j];
-                }
-            }
+        // the rows (targets, then the syndrome rows) in the leaf table's order
+        M.resize((size_t)sg.rows * nin);
+        solve_rows(sg.num.data(), k, nin, sg.tnum.data(), nt, M.data());
+        pack_rows(M.data(), sg.rows, nin, nw, h_coef + eoff[q]);
     }
     hipError_t e = launch_repair_prep(stage, d_descs, (int)nb, c->jt_base, s);
     if (e != hipSuccess) {  // nothing was queued
-        repair_release(c, b, false, s);
+        block_release(c->repair, b, false, s);
         return hip_fail(e);
     }
     const int64_t chunks = piece_len / 16, tiles = (chunks + kTileChunksHost - 1) / kTileChunksHost;
@@ -206,7 +129,7 @@ int repair_call(ec_ctx *c, std::vector<RepairSeg> &segs, int64_t nstripes, int32
         const int nw = segs[idx[q0]].nw;
         size_t q1 = q0;
         // (more tiles than one launch takes: in parts)
-        while (q1 < nb && segs[idx[q1]].nw == nw && (int64_t)(q1 + 1 - q0) * tiles <= repair_max_tiles(nw)) q1++;
+        while (q1 < nb && segs[idx[q1]].nw == nw && (int64_t)(q1 + 1 - q0) * tiles <= share_max_tiles(nw)) q1++;
         RepairArgs a{};
         a.desc = d_descs + q0;
         a.piece_len = piece_len;
@@ -217,7 +140,7 @@ int repair_call(ec_ctx *c, std::vector<RepairSeg> &segs, int64_t nstripes, int32
         e = launch_repair(a, nw, s);
         q0 = q1;
     }
-    repair_release(c, b, true, s);
+    block_release(c->repair, b, true, s);
     if (e != hipSuccess) return hip_fail(e);
     c->last_body = EC_BODY_JUMP_TABLE;
     return after_launch(c->d_chk, s);
@@ -299,13 +222,12 @@ int ec_repair_segments_sets(const ec_ctx *cc, size_t nseg, const int *nshares, c
         for (const uint8_t *p : sg.out) sg.bits = sg.bits && aligned16(p);
         if (sg.bits) {
             const int64_t tiles = ((int64_t)nstripes * (ess / 16) + kTileChunksHost - 1) / kTileChunksHost;
-            if (tiles > repair_max_tiles(sg.nw)) return EC_ERR_UNSUPPORTED;
+            if (tiles > share_max_tiles(sg.nw)) return EC_ERR_UNSUPPORTED;
         }
     }
     DeviceGuard dg(c->device);
     // staging blocks are recycled by events behind launches that run: not under stream capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
     if (check) HIP_TRY(hipMemsetAsync(dev_status, 0, sizeof(int32_t) * nseg, s));
     if (segs.empty()) return EC_OK;
     return repair_call(c, segs, (int64_t)nstripes, dev_status, check, s);

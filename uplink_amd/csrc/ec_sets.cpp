@@ -64,32 +64,6 @@ int set_segment(const ec_ctx *c, int nshares, const int *nums, const uint8_t *co
     return EC_OK;
 }
 
-// The rows of a Rebuild segment as rs_sets_prep solves them (rs_sets.hip,
-// closed-form Lagrange weights through the basis shares' points), into
-// coef[r * nin + j]: missing data position r from basis input j.
-void solve_rows_host(const SetSeg &sg, int k, uint8_t *coef) {
-    uint8_t x[kMaxOps];
-    int lw[kMaxOps];
-    for (int p = 0; p < k; p++) x[p] = gf_point(sg.num[p]);
-    for (int p = 0; p < k; p++) {
-        int l = 0;
-        for (int t = 0; t < k; t++)
-            if (t != p) l += kGf.log[x[p] ^ x[t]];
-        lw[p] = l % 255;
-    }
-    for (int r = 0; r < sg.nstore; r++) {
-        const uint8_t y = gf_point(sg.missing[r]);
-        int ln = 0, hit = -1;
-        for (int t = 0; t < k; t++) {
-            if (y == x[t]) hit = t;
-            else ln += kGf.log[y ^ x[t]];
-        }
-        for (int j = 0; j < k; j++)
-            coef[r * sg.nin + j] = hit >= 0 ? (uint8_t)(hit == j)
-                                            : kGf.exp[(((ln - kGf.log[y ^ x[j]] - lw[j]) % 255) + 255) % 255];
-    }
-}
-
 // The slots' host memory is read by rs_sets_prep and written by the launches'
 // last workgroup straight over the bus: coherent (uncached on the GPU side), so
 // a slot reused by the next call is never read from a stale cache line.
@@ -190,7 +164,7 @@ int sets_call(ec_ctx *c, std::vector<SetSeg> &segs, int64_t nstripes, hipStream_
     }
     {  // more tiles than one launch takes: in parts (each a call of its own)
         const int64_t tiles_seg = (nstripes * (ess / 16) + kTileChunksHost - 1) / kTileChunksHost;
-        const int64_t per = sets_max_tiles(4) / tiles_seg;
+        const int64_t per = share_max_tiles(4) / tiles_seg;
         if (per < 1) return EC_ERR_UNSUPPORTED;
         if ((int64_t)nseg > per) {
             for (size_t g0 = 0; g0 < nseg; g0 += (size_t)per) {
@@ -210,11 +184,10 @@ int sets_call(ec_ctx *c, std::vector<SetSeg> &segs, int64_t nstripes, hipStream_
     size_t words = 0;
     for (size_t q = 0; q < nseg; q++) {
         toff[q] = words;
-        words += (sets_tgt_entries(segs[idx[q]].nin, segs[idx[q]].rows, segs[idx[q]].nw) + 7) & ~(size_t)7;
+        words += (leaf_entries(segs[idx[q]].nin, segs[idx[q]].rows, segs[idx[q]].nw) + 7) & ~(size_t)7;
     }
     // the completion-word protocol needs the launches to run: not under stream capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
     SetsSlot *sl = sets_acquire(c, nseg, words);
     if (!sl) return EC_ERR_DEVICE;
     // one segment: its record goes in the prep launch's arguments (no read over the bus)
@@ -279,7 +252,7 @@ int sets_call(ec_ctx *c, std::vector<SetSeg> &segs, int64_t nstripes, hipStream_
         p.nin = sg.nin;
         p.nout = sg.rows;
         p.nstore = sg.nstore;
-        solve_rows_host(sg, k, p.coef);
+        solve_rows(sg.num, k, sg.nin, sg.missing, sg.nstore, p.coef);  // (Rebuild: nin == k, no syndrome rows)
         e = launch_sets_one(p, sg.nw, s);
         if (e != hipSuccess) {  // nothing was queued
             sets_release(c, sl);

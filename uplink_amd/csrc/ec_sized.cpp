@@ -66,76 +66,6 @@ int prepare_segment(const ec_ctx *c, int nshares, const int *nums, const uint8_t
     return EC_OK;
 }
 
-// Row r of the segment's matrix (nin columns): missing data position r from the
-// basis, then one syndrome row per non-basis input (its prediction from the
-// basis, and 1 on the input itself: the two cancel when the share agrees).
-void solve_rows(const SizedSeg &sg, int k, std::vector<uint8_t> &M) {
-    const int nin = (int)sg.in.size(), nst = (int)sg.missing.size();
-    const LagrangeBasis L(sg.num.data(), k);
-    M.assign((size_t)std::max(sg.rows, 1) * nin, 0);
-    for (int r = 0; r < sg.rows; r++) {
-        L.row(gf_point(r < nst ? sg.missing[r] : sg.num[k + r - nst]), &M[(size_t)r * nin]);
-        if (r >= nst) M[(size_t)r * nin + k + r - nst] = 1;
-    }
-}
-
-size_t pow2_at_least(size_t n, size_t lo) {
-    size_t c = lo;
-    while (c < n) c *= 2;
-    return c;
-}
-
-// A block of the context's sized pool with room for h_need pinned and d_need
-// device bytes whose previous pass has finished on the GPU, or a new one (sized
-// in powers of two).  nullptr: no memory.  (RepairBlock's mechanism, ec_repair.cpp.)
-RepairBlock *sized_acquire(ec_ctx *c, size_t h_need, size_t d_need) {
-    RepairPool &P = c->sized;
-    RepairBlock *b = nullptr, *oldest = nullptr;
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        for (auto &x : P.blocks) {
-            if (x->busy) continue;
-            if (x->h_cap < h_need || x->d_cap < d_need) continue;
-            if (!oldest) oldest = x.get();
-            if (x->idle()) {
-                b = x.get();
-                break;
-            }
-        }
-        if (!b && P.blocks.size() >= RepairPool::kMaxBlocks) b = oldest;  // waited for below
-        if (!b) {
-            auto x = std::make_unique<RepairBlock>();
-            x->h_cap = pow2_at_least(h_need, 64u << 10);
-            x->d_cap = pow2_at_least(d_need, 512u << 10);
-            if (hipHostMalloc((void **)&x->h, x->h_cap, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-                hipMalloc((void **)&x->d, x->d_cap) != hipSuccess ||
-                hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess)
-                return nullptr;  // (its destructor frees what it got)
-            P.blocks.push_back(std::move(x));
-            b = P.blocks.back().get();
-        }
-        b->busy = true;
-    }
-    if (b->queued && hipEventSynchronize(b->ev) != hipSuccess) {
-        std::lock_guard<std::mutex> g(P.mu);
-        b->busy = false;
-        return nullptr;
-    }
-    b->queued = false;
-    return b;
-}
-
-// Hand the block back; `launched`: something that reads it was queued on s.
-void sized_release(ec_ctx *c, RepairBlock *b, bool launched, hipStream_t s) {
-    // (an event that cannot be recorded leaves the block to a wait for the stream)
-    if (launched && hipEventRecord(b->ev, s) != hipSuccess) (void)hipStreamSynchronize(s);
-    std::lock_guard<std::mutex> g(c->sized.mu);
-    b->queued = launched;
-    b->busy = false;
-}
-
-size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // One pass over segs[0..n): rs_sized_prep, then the tile kernel per wave-count
 // class (in parts where a class has more tiles than a launch takes), all on
 // stream s.  With `bad` (Decode), waits and returns per segment the count of
@@ -151,16 +81,16 @@ int sized_pass(ec_ctx *c, SizedSeg *const *segs, size_t n, hipStream_t s, std::v
         nw[i] = segs[i]->nw;
         tiles[i] = segs[i]->tiles;
     }
-    const sized::Layout L = sized::layout(nw.data(), tiles.data(), n, sets_max_tiles);
+    const sized::Layout L = sized::layout(nw.data(), tiles.data(), n, share_max_tiles);
     std::vector<size_t> eoff(n + 1, 0);
     for (size_t q = 0; q < n; q++) {
         const SizedSeg &sg = *segs[L.idx[q]];
-        eoff[q + 1] = eoff[q] + sized_tgt_entries((int)sg.in.size(), sg.rows, sg.nw);
+        eoff[q + 1] = eoff[q] + staged_entries((int)sg.in.size(), sg.rows, sg.nw);
     }
     const size_t h_stage = up(n * sizeof(SizedStage), 16), h_coef_len = eoff[n];
     const size_t d_desc = up(n * sizeof(SizedDesc), 256), d_tgt_len = eoff[n] * 8;
     const size_t d_map_len = up((size_t)L.map_entries * 4, 256);
-    RepairBlock *b = sized_acquire(c, h_stage + h_coef_len + n * 4, d_desc + d_tgt_len + d_map_len + n * 4);
+    StageBlock *b = block_acquire(c->sized, h_stage + h_coef_len + n * 4, d_desc + d_tgt_len + d_map_len + n * 4);
     if (!b) return EC_ERR_DEVICE;
     SizedStage *stage = (SizedStage *)b->h;
     uint8_t *h_coef = b->h + h_stage;
@@ -194,24 +124,14 @@ int sized_pass(ec_ctx *c, SizedSeg *const *segs, size_t n, hipStream_t s, std::v
         st.entries = (int64_t)(eoff[q + 1] - eoff[q]);
         st.map = d_map + L.map_off[q] + L.tile0[q];
         st.ntiles = sg.tiles;
-        // the coefficients in the leaf table's order: [pass][input][group][8], a group's rows right-aligned
-        solve_rows(sg, k, M);
-        uint8_t *cf = h_coef + eoff[q];
-        memset(cf, 0, (size_t)st.entries);
-        const int npass = sized_npass(sg.rows, w);
-        for (int pass = 0; pass < npass; pass++)
-            for (int g = 0; g < w; g++) {
-                int rb, cn;
-                sized_rows_of(pass, npass, sg.rows, w, g, rb, cn);
-                for (int j = 0; j < nin; j++) {
-                    uint8_t *e = cf + (((size_t)pass * nin + j) * w + g) * 8 + (8 - cn);
-                    for (int o = 0; o < cn; o++) e[o] = M[(size_t)(rb + o) * nin + j];
-                }
-            }
+        // the rows (missing data positions, then the syndrome rows) in the leaf table's order
+        M.resize((size_t)std::max(sg.rows, 1) * nin);
+        solve_rows(sg.num.data(), k, nin, sg.missing.data(), nst, M.data());
+        pack_rows(M.data(), sg.rows, nin, w, h_coef + eoff[q]);
     }
     hipError_t e = launch_sized_prep(stage, d_descs, (int)n, c->jt_base, s);
     if (e != hipSuccess) {  // nothing was queued
-        sized_release(c, b, false, s);
+        block_release(c->sized, b, false, s);
         return hip_fail(e);
     }
     for (const sized::Launch &ln : L.launches) {
@@ -234,7 +154,7 @@ int sized_pass(ec_ctx *c, SizedSeg *const *segs, size_t n, hipStream_t s, std::v
         bad->assign(n, 0);
         for (size_t q = 0; q < n && e == hipSuccess; q++) (*bad)[L.idx[q]] = h_cnt[q];
     }
-    sized_release(c, b, true, s);
+    block_release(c->sized, b, true, s);
     if (e != hipSuccess) return hip_fail(e);
     c->last_body = EC_BODY_JUMP_TABLE;
     return after_launch(c->d_chk, s);
@@ -271,8 +191,7 @@ int sized_call(ec_ctx *c, size_t nseg, const int *nshares, const int *nums, cons
         for (int i = 0; i < ns; i++) sg.bits = sg.bits && aligned16(sp[i]);
     }
     // staging blocks are recycled by events behind launches that run: not under stream capture
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return EC_ERR_UNSUPPORTED;
+    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
     *queued = true;
     std::vector<int> rcs(nseg, EC_OK);
     // A segment's own outcome.  Too few shares is an argument error of the call, found above

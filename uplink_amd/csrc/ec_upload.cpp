@@ -108,8 +108,8 @@ int ec_upload_begin(const ec_ctx *cc, const uint8_t *seg, size_t nstripes, uint8
     const bool streamed_hash = hashed && upload_hash_streamed(c, u->end, nstripes);
     const uint64_t nb3 = (plen + 1023) / 1024;  // BLAKE3 chunks per piece
     // hash area: [n][nb3][8] chunk CVs | n*32 hashes | scratch (fold, or the one-pass hash's)
-    const size_t cvs_bytes = streamed_hash ? align_up((size_t)c->n * nb3 * 32, 256) : 0;
-    const size_t hash_bytes = align_up(32 * (size_t)c->n, 256);
+    const size_t cvs_bytes = streamed_hash ? up((size_t)c->n * nb3 * 32, 256) : 0;
+    const size_t hash_bytes = up(32 * (size_t)c->n, 256);
     const size_t scratch = streamed_hash ? b3_fold_ws_bytes(c->n, nb3) : b3_segment_ws_bytes(c, 1, nstripes);
     const size_t hcap = hashed ? cvs_bytes + hash_bytes + std::max<size_t>(scratch, 256) : 0;
     {

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rs_args.hpp"
+#include "rs_rows.hpp"
 
 namespace uplink_ec {
 
@@ -50,12 +51,8 @@ struct RepairArgs {
 // waves per workgroup for `rows` computed rows: as sets_waves up to 32 rows, 8
 // waves above (up to 64 rows in one pass over the inputs)
 int repair_waves(int rows);
-// bytes (= entries) of one segment's coefficient staging and 64-bit words of its leaf table on nw waves
-size_t repair_tgt_entries(int nin, int rows, int nw);
-// the rows group g of nw computes in pass `pass` of npass (rs_sets.hip rows_of)
-void repair_rows_of(int pass, int npass, int nout, int nw, int g, int &rbase, int &cnt);
-int repair_npass(int nout, int nw);
-int64_t repair_max_tiles(int nw);
+// (one segment's coefficient staging and leaf table on nw waves: staged_entries bytes and words;
+// a launch: at most share_max_tiles(nw) tiles -- rs_rows.hpp)
 hipError_t launch_repair_prep(const RepairStage *stage, RepairDesc *desc, int nseg, uint64_t jt_base, hipStream_t s);
 hipError_t launch_repair(const RepairArgs &a, int nw, hipStream_t s);
 // byte path with the share check: the rows of `a` (coef, in_off, nin, nout as

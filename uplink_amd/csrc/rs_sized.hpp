@@ -4,9 +4,9 @@
 // sizes as there are objects (private/ecclient/client.go:302-303 sizes each
 // from its own `size`), and one stream-ordered pass serves them all.
 //
-// The tile body is rs_matmul_sets' (rs_sets.hip) with the geometry it takes
-// from the launch -- stripes, chunks and tiles per segment -- read from the
-// tile's segment descriptor instead.  A tile finds its segment through a map
+// The tile body is the one rs_matmul_sets runs (rs_sets_tile.hpp) with the
+// geometry that kernel takes from the launch -- stripes, chunks and tiles per
+// segment -- read from the tile's segment descriptor instead.  A tile finds its segment through a map
 // of the launch's class: one uint32 per tile, the position of its segment's
 // descriptor in the pass.  Per pass the host writes, per segment, a SizedStage
 // into pinned memory (the descriptor, the rows' coefficients in leaf-table
@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rs_args.hpp"
+#include "rs_rows.hpp"
 
 namespace uplink_ec {
 
@@ -59,13 +60,9 @@ struct SizedArgs {
     uint32_t *chk_flag;     // checked build: first access outside a share / an output (site 12 or 13)
 };
 
-// bytes (= entries) of one segment's coefficient staging and 64-bit words of its leaf table on nw waves
-size_t sized_tgt_entries(int nin, int rows, int nw);
-// the rows group g of nw computes in pass `pass` of npass (rs_sets.hip rows_of)
-void sized_rows_of(int pass, int npass, int nout, int nw, int g, int &rbase, int &cnt);
-int sized_npass(int nout, int nw);
+// (one segment's coefficient staging and leaf table on nw waves: staged_entries bytes and words, rs_rows.hpp)
 hipError_t launch_sized_prep(const SizedStage *stage, SizedDesc *desc, int nseg, uint64_t jt_base, hipStream_t s);
-// nw: 2, 3 or 4 (sets_waves); at most sets_max_tiles(nw) tiles
+// nw: 2, 3 or 4 (sets_waves); at most share_max_tiles(nw) tiles
 hipError_t launch_matmul_sized(const SizedArgs &a, int nw, hipStream_t s);
 
 }  // namespace uplink_ec
