@@ -35,6 +35,8 @@
  *                            callers of ecclient.Client do with Get + PutSingleResult /
  *                            PutPiece (ecclient/client.go:36-44,77-101), without the
  *                            decoded segment in between
+ *   ec_repair_segments_sized the same with a stripe count per segment: a repair queue
+ *                            holds segments of as many sizes as there are objects
  *   ec_*_segments_host       the same batches from/to host memory (PCIe pipeline)
  *   ec_*blake3* / ec_hash_segments / ec_encode_segments_host_hashed
  *                            BLAKE3 piece hash of the upload (piecestore/upload.go:
@@ -305,6 +307,37 @@ int ec_repair_segments_sets(const ec_ctx *ctx, size_t nseg, const int *nshares, 
                             const uint8_t *const *pieces, const int *ntargets, const int *targets,
                             uint8_t *const *outs, size_t nstripes, int flags, int32_t *dev_status,
                             ec_stream stream);
+/* ec_repair_segments_sets with a stripe count per segment: a repair queue holds
+ * segments of as many sizes as there are objects, and one stream-ordered pass
+ * serves them all.  Segment g has nstripes[g] stripes: its shares and its
+ * outputs are nstripes[g]*ess bytes each.  Everything else is as above: shares,
+ * targets and outputs flattened per segment, the basis infectious Rebuild's
+ * choice, the rows solved on the host and staged in an event-recycled block,
+ * async on stream, no host synchronisation, no caller memory retained.  Each
+ * 2048-column tile finds its segment through a per-launch map, as in
+ * ec_rebuild_segments_sized; a batch of thousands of segments goes in passes of
+ * bounded staging, and a class of more tiles than one launch takes in several
+ * launches, so no segment is too long for the call other than by the limit
+ * below.
+ *
+ * Every segment is validated before anything is queued: on an argument error
+ * nothing is written and no status word is touched.  The errors are those of
+ * ec_repair_segments_sets, and a segment whose nstripes[g]*ess/16 does not fit
+ * 32 bits: EC_ERR_UNSUPPORTED.  nstripes[g] == 0 or ntargets[g] == 0 skips
+ * segment g: its entries of nums, pieces, targets and outs are stepped over and
+ * otherwise not looked at (they may be NULL).  With EC_FLAG_CHECK_SHARES
+ * (at most 128 shares per segment) dev_status[g] is as above, and a skipped
+ * segment's word is zeroed like the others.
+ *
+ * Segments whose share size is no multiple of 16, or with a share or output
+ * pointer that is not 16-byte aligned, go one by one through the byte kernel
+ * with their own stripe count; same results, and the other segments of the
+ * call stay in the pass.  Up to k = 128.  Not under stream capture
+ * (EC_ERR_UNSUPPORTED). */
+int ec_repair_segments_sized(const ec_ctx *ctx, size_t nseg, const int *nshares, const int *nums,
+                             const uint8_t *const *pieces, const int *ntargets, const int *targets,
+                             uint8_t *const *outs, const size_t *nstripes, int flags, int32_t *dev_status,
+                             ec_stream stream);
 /* ec_rebuild_segments[_batched] with a share set the context has no
  * straight-line code for runs the share-set pass and has the code made in the
  * background (DESIGN.md §4 "Straight-line rebuild bodies"); later launches of

@@ -87,6 +87,11 @@ SIGNATURES = {
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(vp), ctypes.c_size_t, ctypes.c_int, vp, vp]),
+    "ec_repair_segments_sized": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
+                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),
+                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, vp,
+                                                vp]),
     "ec_prepare_rebuild": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "ec_encode_segments_host": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_int]),
     "ec_rebuild_segments_host": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(vp),

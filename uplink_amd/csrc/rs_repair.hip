@@ -12,6 +12,10 @@
 //      pieces in and pieces out (RepairGeom); NW = 8 takes up to 64 rows in one
 //      pass over the inputs.  Rows from nstore on are syndrome rows (the share
 //      check): OR-reduced over the valid columns, never stored.
+//  rs_repair_sized_prep, rs_repair_sized<NW>: the same for segments of
+//      different sizes in one launch (RepairSizedGeom): the prep kernel also
+//      fills the segment's range of its class's tile map, and a workgroup finds
+//      its segment through that map, as rs_matmul_sized does (rs_sized.hip).
 #include <hip/hip_runtime.h>
 
 #include "gf256_field.hpp"
@@ -82,6 +86,76 @@ __global__ __launch_bounds__(NW * 64, 4) void rs_repair(const RepairArgs a) {
     share_tile<NW>(G);
 }
 
+// ---- segments of different sizes (ec_repair_segments_sized) ----
+
+__global__ __launch_bounds__(256) void rs_repair_sized_prep(const RepairSizedStage *stage, RepairSizedDesc *desc,
+                                                            uint64_t jt_base) {
+    const RepairSizedStage *st = stage + blockIdx.x;
+    copy_desc(&st->d, desc + blockIdx.x);
+    // the segment's tiles of its class's map: all this segment
+    uint32_t *map = st->map;
+    const int64_t ntiles = st->ntiles;
+    for (int64_t i = threadIdx.x; i < ntiles; i += blockDim.x) map[i] = blockIdx.x;
+    write_leaves(st->coef, st->entries, st->d.tgt, jt_base);
+}
+
+// The map and the descriptors are read through the constant address space: the
+// kernel never writes them, and uniform loads from there are scalar loads.
+typedef const __attribute__((address_space(4))) RepairSizedDesc ConstSizedDesc;
+typedef const __attribute__((address_space(4))) uint32_t ConstMap;
+
+// RepairGeom with the segment found through the class's map (as SizedGeom finds
+// it, rs_sized.hip) and the tile, the ragged end and the extents taken from the
+// segment's own descriptor.
+struct RepairSizedGeom {
+    static constexpr bool kCopy = false, kOwnTable = false;
+    const RepairSizedArgs &a;
+    ConstSizedDesc *d;
+    const int64_t tile;  // the workgroup's tile within its segment
+    const int nstore;
+    bool vA, vB;
+    int64_t iA, iB, oA, oB;
+    uint32_t bad = 0;
+
+    // ctile: the workgroup's tile of the class; its segment through the map
+    __device__ __forceinline__ RepairSizedGeom(const RepairSizedArgs &a_, int64_t ctile)
+        : a(a_),
+          d((ConstSizedDesc *)(a_.desc + (uint32_t)__builtin_amdgcn_readfirstlane(((ConstMap *)a_.map)[ctile]))),
+          tile(ctile - d->tile0), nstore(d->nstore) {}
+    __device__ __forceinline__ bool skip(int nin, int nout) const { return nin <= 0 || nout <= 0 || tile < 0; }
+    __device__ __forceinline__ void cols(int lane) {
+        const int64_t chunks = d->chunks;
+        const int64_t qA = tile * kTileChunks + lane, qB = qA + 64;
+        vA = qA < chunks, vB = qB < chunks;
+        // a lane past the end of the piece reads column 0 of its own segment's share (never
+        // stored, masked out of the check)
+        iA = vA ? qA * 16 : 0, iB = vB ? qB * 16 : 0;
+        oA = qA * 16, oB = qB * 16;
+    }
+    __device__ __forceinline__ bool in_ok(const uint8_t *p, const uint8_t *share) const {
+        return in_span(a, p, share, d->piece_len, 14);
+    }
+    __device__ __forceinline__ bool out_ok(const uint8_t *p, const uint8_t *row) const {
+        return in_span(a, p, row, d->piece_len, 15);
+    }
+    __device__ __forceinline__ uint8_t *row_out(int r) const { return d->out[r]; }
+    __device__ __forceinline__ int stored(int, int) const { return nstore; }
+    __device__ __forceinline__ bool checks(int rbase, int cnt, int nst) const { return rbase + cnt > nst; }
+    __device__ __forceinline__ void report(uint32_t any, int) { bad |= any; }
+    __device__ __forceinline__ void finish(int lane) const {
+        if (d->nout > nstore) {
+            int32_t *st = d->status;
+            if (__ballot(bad != 0) != 0 && lane == 0 && st) atomicOr(st, 1);
+        }
+    }
+};
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 4) void rs_repair_sized(const RepairSizedArgs a) {
+    RepairSizedGeom G(a, a.tile_base + blockIdx.x);
+    share_tile<NW>(G);
+}
+
 // The byte path's share check: row r of the launch's matrix, computed as
 // rs_matmul_bytes computes it, against the share at out_off[r].
 __global__ __launch_bounds__(256) void rs_repair_check_bytes(const RsArgs a) {
@@ -122,6 +196,18 @@ hipError_t launch_repair_prep(const RepairStage *stage, RepairDesc *desc, int ns
 
 hipError_t launch_repair(const RepairArgs &a, int nw, hipStream_t s) {
     return launch_share_tile(a, a.total_tiles, nw, s, rs_repair<2>, rs_repair<3>, rs_repair<4>, rs_repair<8>);
+}
+
+hipError_t launch_repair_sized_prep(const RepairSizedStage *stage, RepairSizedDesc *desc, int nseg, uint64_t jt_base,
+                                    hipStream_t s) {
+    if (nseg <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rs_repair_sized_prep, dim3(nseg), dim3(256), 0, s, stage, desc, jt_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_repair_sized(const RepairSizedArgs &a, int nw, hipStream_t s) {
+    return launch_share_tile(a, a.total_tiles, nw, s, rs_repair_sized<2>, rs_repair_sized<3>, rs_repair_sized<4>,
+                             rs_repair_sized<8>);
 }
 
 hipError_t launch_repair_check_bytes(const RsArgs &a, hipStream_t s) {

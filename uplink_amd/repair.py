@@ -13,6 +13,9 @@ segments in one stream-ordered pass.
                        with every surplus share checked against the basis, flagged
                        segments corrected through Decode and repaired again; and
                        the BLAKE3 piece hashes PutPiece sends, piecestore/upload.go:270)
+  repair_segments_sized  the same for segments of different sizes in one call
+                       (ec_repair_segments_sized): a repair queue holds segments of as
+                       many sizes as there are objects
   SegmentRepairer      which pieces to regenerate, by ecclient.put's threshold rule
                        (client.go:113-116), and the repair of those
 """
@@ -141,6 +144,112 @@ def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces
         return outs, hashes
 
 
+def repair_call_sized(ctx, segments, out_ptrs: Sequence[int], nstripes_list: Sequence[int], flags: int = 0, status=None,
+                      stream=None) -> int:
+    """ec_repair_segments_sized on raw arguments; returns its code.  As
+    repair_call with a stripe count per segment."""
+    nsh, nums, ptrs, ntg, tgts = _flatten(segments)
+    out_ptrs = [SegmentCodec._addr(p) for p in out_ptrs]
+    if len(out_ptrs) != len(tgts):
+        raise ValueError("one output per target")
+    nstripes_list = [int(x) for x in nstripes_list]
+    if len(nstripes_list) != len(nsh):
+        raise ValueError("one stripe count per segment")
+    if any(x < 0 for x in nstripes_list):
+        raise ValueError("a negative stripe count")
+    return N.load().ec_repair_segments_sized(
+        ctx, len(nsh), _carr(ctypes.c_int, nsh), _carr(ctypes.c_int, nums), _carr(ctypes.c_void_p, ptrs),
+        _carr(ctypes.c_int, ntg), _carr(ctypes.c_int, tgts), _carr(ctypes.c_void_p, out_ptrs),
+        _carr(ctypes.c_size_t, nstripes_list), flags, SegmentCodec._addr(status) if status is not None else None,
+        SegmentCodec._stream(stream))
+
+
+def _sizes_of(scheme_or_ctx, ctx):
+    """(ess, k) of a scheme or of a raw context"""
+    if hasattr(scheme_or_ctx, "erasure_share_size"):
+        return scheme_or_ctx.erasure_share_size(), scheme_or_ctx.required_count()
+    lib = N.load()
+    return lib.ec_share_size(ctx), lib.ec_required(ctx)
+
+
+def repair_segments_sized(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, stream=None):
+    """repair_segments for segments of different sizes, in one engine call
+    (ec_repair_segments_sized): a repair queue holds segments of as many sizes
+    as there are objects.  Each segment's piece length is that of its own
+    tensors; lengths that differ within one segment are EC_ERR_SHARE_SIZE, a
+    length that is no multiple of the share size EC_ERR_INVALID_ARG, both
+    raised before anything is queued.  Returns, per segment, its own
+    [len(targets), piece_len] uint8 device tensor (with hash_pieces, also the
+    [len(targets), 32] hashes), each allocated on its own.
+
+    check: as repair_segments; flagged segments are corrected through Decode
+    with their own stripe count and repaired again in one sized call."""
+    import torch
+
+    ctx = _ctx_of(scheme_or_ctx)
+    segments = [(list(a), list(b), list(c)) for a, b, c in segments]
+    ess, k = _sizes_of(scheme_or_ctx, ctx)
+    if ess <= 0 or k <= 0:
+        _raise(None, N.EC_ERR_INVALID_ARG)
+    plens, dev = [], None
+    for _, pieces, _ in segments:
+        plen = pieces[0].numel() if pieces else 0
+        for p in pieces:
+            if p.numel() != plen:
+                _raise(ctx, N.EC_ERR_SHARE_SIZE)
+        if plen % ess:
+            _raise(ctx, N.EC_ERR_INVALID_ARG)
+        if pieces and dev is None:
+            dev = pieces[0].device
+        plens.append(plen)
+    if dev is None:
+        return ([], []) if hash_pieces else []
+    lib = N.load()
+    stripes = [p // ess for p in plens]
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        # one allocation per segment: each is 16-byte aligned, so each stays in the pass
+        outs = [torch.empty((len(t), p), dtype=torch.uint8, device=dev) for (_, _, t), p in zip(segments, plens)]
+        rows = [o[i] for o in outs for i in range(o.shape[0])]
+        status = torch.empty(len(segments), dtype=torch.int32, device=dev) if check else None
+        flags = N.EC_FLAG_CHECK_SHARES if check else 0
+        _raise(ctx, repair_call_sized(ctx, segments, rows, stripes, flags, status, stream))
+
+        def read(t):  # (waits for the stream; a raw stream handle is not one torch's copy follows)
+            if stream is not None and ts is None:
+                torch.cuda.synchronize()
+            return t.cpu().tolist()
+
+        if check:
+            bad = [g for g, s in enumerate(read(status)) if s]
+            if bad:
+                scratch = torch.empty(max(plens[g] for g in bad) * k, dtype=torch.uint8, device=dev)
+                st = SegmentCodec._stream(stream)
+                for g in bad:
+                    nums, pieces, _ = segments[g]
+                    rc = lib.ec_decode_segments(ctx, len(nums), _carr(ctypes.c_int, nums),
+                                                _carr(ctypes.c_void_p, [p.data_ptr() for p in pieces]), stripes[g],
+                                                scratch.data_ptr(), st)
+                    _raise(ctx, rc)
+                again = [segments[g] for g in bad]
+                st2 = torch.empty(len(bad), dtype=torch.int32, device=dev)
+                rows2 = [outs[g][i] for g in bad for i in range(outs[g].shape[0])]
+                _raise(ctx, repair_call_sized(ctx, again, rows2, [stripes[g] for g in bad], flags, st2, stream))
+                if any(read(st2)):  # (corrected shares are codewords: not expected)
+                    _raise(ctx, N.EC_ERR_TOO_MANY_ERRORS)
+        if not hash_pieces:
+            return outs
+        # every regenerated row of the batch in one list call, a length per piece
+        from .piecehash import blake3_pieces_list
+        flat = blake3_pieces_list(ctx, rows, stream=stream) if rows else None
+        hashes, at = [], 0
+        for o in outs:
+            cnt = o.shape[0]
+            hashes.append(flat[at:at + cnt] if cnt else torch.empty((0, 32), dtype=torch.uint8, device=dev))
+            at += cnt
+        return outs, hashes
+
+
 class _Null:
     def __enter__(self):
         return self
@@ -192,13 +301,22 @@ class SegmentRepairer:
         healthy pieces.  Returns per segment a dict {piece number: regenerated
         tensor} (empty where no repair is needed); with hash_pieces, also a dict
         {piece number: 32-byte hash tensor} per segment."""
+        return self._repair(repair_segments, segments, check, hash_pieces, stream)
+
+    def repair_sized(self, segments: Sequence[Dict[int, object]], *, check: bool = False, hash_pieces: bool = False,
+                     stream=None):
+        """repair for segments of different sizes (repair_segments_sized): each
+        segment's pieces have the segment's own length."""
+        return self._repair(repair_segments_sized, segments, check, hash_pieces, stream)
+
+    def _repair(self, call, segments, check, hash_pieces, stream):
         batch, tg = [], []
         for seg in segments:
             nums = list(seg.keys())
             t = self.targets(nums)
             tg.append(t)
             batch.append((nums, [seg[x] for x in nums], t))
-        res = repair_segments(self.rs, batch, check=check, hash_pieces=hash_pieces, stream=stream)
+        res = call(self.rs, batch, check=check, hash_pieces=hash_pieces, stream=stream)
         outs, hashes = res if hash_pieces else (res, None)
         pieces = [{t: o[i] for i, t in enumerate(ts)} for ts, o in zip(tg, outs)]
         if not hash_pieces:
