@@ -44,6 +44,8 @@
  *   ec_blake3_pieces_list / ec_hash_segments_sized
  *                            the same with a length per piece: the hashes of a batch of
  *                            uploads of different sizes in one pass
+ *   ec_sha256_*              the SHA-256 piece hash (pb.PieceHashAlgorithm_SHA256,
+ *                            hash.go:15-26): a list, a sized batch, pieces of one length
  *   ec_gcm_*                 AES-256-GCM segment encryption: splitter/splitter.go:156,170
  *                            (upload), streams/store.go:347-382 (download), SURVEY §8f row 4
  *   ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized
@@ -464,6 +466,61 @@ int ec_hash_list_stats(const ec_ctx *ctx, unsigned long long *fast, unsigned lon
                        unsigned long long *parents, unsigned long long *oversize);
 /* Host buffers, synchronous: hashes[32*j] = BLAKE3(data + j*stride, piece_len) */
 int ec_blake3_host(const uint8_t *data, size_t npieces, long long stride, size_t piece_len, uint8_t *hashes);
+
+/* ---- SHA-256 piece hashes (pb.PieceHashAlgorithm_SHA256, hash.go:15-26) ----
+ * The other value of the upload's piece hash algorithm, the protobuf zero value
+ * and the legacy one (WithPieceHashAlgo overrides the BLAKE3 default,
+ * piecestore/hash.go:20-26; upload.go:133,155,270).  FIPS 180-4, 32-byte
+ * digests.  SHA-256 is one serial chain per piece: a piece is one lane of a
+ * kernel, so a call is as fast as it has pieces -- one piece is never fast, a
+ * batch of segments is thousands of chains.  A launch advances every piece by
+ * at most 16,384 blocks (1 MiB), the state carried in device memory between the
+ * launches of a call, so every kernel stays short and a piece of any length up
+ * to 2^61 - 1 bytes takes the same path (longer: EC_ERR_UNSUPPORTED).  A piece
+ * with a 16-byte aligned base and run stride that is contiguous or has runs of
+ * a power of two >= 64 bytes is read with 16-byte loads, any other byte by
+ * byte; both kinds share a call.
+ * The calls have their BLAKE3 siblings' rules: everything is validated before
+ * anything is queued, on an argument error nothing is written, async on stream,
+ * no caller memory retained; the list calls stage in the same event-recycled
+ * pool and are not for a capturing stream (EC_ERR_UNSUPPORTED). */
+#define EC_HASH_SHA256 0 /* pb.PieceHashAlgorithm values */
+#define EC_HASH_BLAKE3 1
+
+/* SHA-256 of npieces contiguous device pieces, piece i at pieces[i] with
+ * lens[i] bytes; hashes: npieces*32 device bytes, row i = piece i.
+ * lens[i] == 0 gives the digest of the empty message, and pieces[i] may then be
+ * NULL; a NULL pieces[i] with lens[i] > 0: EC_ERR_INVALID_ARG.  NULL hashes,
+ * pieces or lens with npieces > 0: EC_ERR_INVALID_ARG.  npieces == 0: EC_OK,
+ * nothing queued. */
+int ec_sha256_pieces_list(const ec_ctx *ctx, size_t npieces, const uint8_t *const *pieces, const size_t *lens,
+                          uint8_t *hashes, ec_stream stream);
+/* All n piece hashes of a batch encoded by ec_encode_segments_sized: same
+ * segs / nstripes / pieces / flags as that call, and ec_hash_segments_sized's
+ * contract.  hashes: [nseg][n][32] device.  With EC_FLAG_PARITY_ONLY data piece
+ * j is read from segs[g] in place (runs of ess bytes, k*ess apart).
+ * nstripes[g] == 0 skips segment g: its pointers may be NULL and its n*32 hash
+ * bytes are left untouched.  A NULL pointer of a segment that is not skipped:
+ * EC_ERR_INVALID_ARG. */
+int ec_sha256_segments_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *const *segs, const size_t *nstripes,
+                             const uint8_t *const *pieces, int flags, uint8_t *hashes, ec_stream stream);
+/* Device pieces of one length, addressed as ec_blake3_pieces addresses them:
+ * byte t of piece j at base + j*piece_stride + (t / run)*run_stride + t % run
+ * (run = piece_len or 0 for contiguous pieces).  hashes: npieces*32 device
+ * bytes.  Needs no context; async on stream (pieces of more than 1 MiB take
+ * npieces*32 bytes of scratch from hipMallocAsync on that stream). */
+int ec_sha256_pieces(const uint8_t *base, size_t npieces, long long piece_stride, size_t piece_len, size_t run,
+                     long long run_stride, uint8_t *hashes, ec_stream stream);
+/* Host buffers, synchronous: hashes[32*j] = SHA-256(data + j*stride, piece_len) */
+int ec_sha256_host(const uint8_t *data, size_t npieces, long long stride, size_t piece_len, uint8_t *hashes);
+/* A diagnostic: the blocks one launch of the two list calls advances a piece by
+ * on this ctx (0 restores the default, 16,384).  Same digests at any value. */
+int ec_sha256_set_launch_blocks(ec_ctx *ctx, size_t blocks);
+/* Work of the two list calls on this ctx so far (a diagnostic): pieces read with
+ * 16-byte loads, pieces read byte by byte, and kernel launches over them.  Any
+ * pointer may be NULL.  No reference counterpart. */
+int ec_sha256_list_stats(const ec_ctx *ctx, unsigned long long *fast, unsigned long long *bytewise,
+                         unsigned long long *launches);
 
 /* ---- AES-256-GCM segment encryption (storj.io/common/encryption, EncAESGCM) ----
  * Replace encryption.TransformWriterPadded(buf, NewEncrypter(EncAESGCM, key,

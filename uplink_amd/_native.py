@@ -107,6 +107,16 @@ SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(vp), ctypes.c_int, vp, vp]),
     "ec_hash_list_stats": (ctypes.c_int, [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 4),
     "ec_blake3_host": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_size_t, vp]),
+    "ec_sha256_pieces_list": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                             vp, vp]),
+    "ec_sha256_segments_sized": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp),
+                                                ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(vp), ctypes.c_int, vp,
+                                                vp]),
+    "ec_sha256_pieces": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_size_t,
+                                        ctypes.c_longlong, vp, vp]),
+    "ec_sha256_host": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_size_t, vp]),
+    "ec_sha256_set_launch_blocks": (ctypes.c_int, [vp, ctypes.c_size_t]),
+    "ec_sha256_list_stats": (ctypes.c_int, [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 3),
     "ec_gcm_key_bytes": (ctypes.c_size_t, []),
     "ec_gcm_prepare_keys": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp]),
     "ec_gcm_seal_segments": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]),

@@ -8,16 +8,11 @@
 // on the call path waits for the stream.
 #include "b3_list_geom.hpp"
 #include "ec_internal.hpp"
+#include "hash_list.hpp"
 
 namespace uplink_ec {
 namespace capi {
 namespace {
-
-// One piece to hash and where its 32 bytes go.
-struct HashPiece {
-    b3list::Piece p;
-    uint8_t *hash;
-};
 
 // One pass over pieces[0..n) (classes cls): staging, then at most two chunk
 // launches and one parents launch on s.
@@ -118,13 +113,9 @@ int ec_blake3_pieces_list(const ec_ctx *cc, size_t npieces, const uint8_t *const
     ec_ctx *c = const_cast<ec_ctx *>(cc);
     if (!c || (npieces && (!pieces || !lens || !hashes))) return EC_ERR_INVALID_ARG;
     if (npieces == 0) return EC_OK;
-    if (npieces > SIZE_MAX / 32) return EC_ERR_INVALID_ARG;
     // every piece is validated before anything is queued
-    std::vector<HashPiece> list(npieces);
-    for (size_t i = 0; i < npieces; i++) {
-        if (!pieces[i] && lens[i]) return EC_ERR_INVALID_ARG;
-        list[i] = {{(uint64_t)(uintptr_t)pieces[i], (uint64_t)lens[i], 0, 0}, hashes + 32 * i};
-    }
+    std::vector<HashPiece> list;
+    if (int rc = list_pieces(npieces, pieces, lens, hashes, list)) return rc;
     DeviceGuard dg(c->device);
     return hash_list(c, list, hashes, hashes + 32 * npieces, (hipStream_t)stream);
 }
@@ -134,30 +125,11 @@ int ec_hash_segments_sized(const ec_ctx *cc, size_t nseg, const uint8_t *const *
     ec_ctx *c = const_cast<ec_ctx *>(cc);
     if (!c || (nseg && (!nstripes || !pieces || !hashes))) return EC_ERR_INVALID_ARG;
     if (nseg == 0) return EC_OK;
-    const size_t k = c->k, n = c->n, ess = c->ess;
-    const bool parity_only = (flags & EC_FLAG_PARITY_ONLY) != 0;
-    if (nseg > SIZE_MAX / (32 * n)) return EC_ERR_INVALID_ARG;
     // every segment is validated before anything is queued
     std::vector<HashPiece> list;
-    list.reserve(nseg * n);
-    for (size_t g = 0; g < nseg; g++) {
-        if (nstripes[g] == 0) continue;
-        if (nstripes[g] > (SIZE_MAX / ess) / n) return EC_ERR_UNSUPPORTED;
-        const uint64_t plen = (uint64_t)nstripes[g] * ess;
-        if (parity_only ? (!segs || !segs[g] || (n > k && !pieces[g])) : !pieces[g]) return EC_ERR_INVALID_ARG;
-        uint8_t *h = hashes + 32 * n * g;
-        for (size_t j = 0; j < n; j++) {
-            if (!parity_only)
-                list.push_back({{(uint64_t)(uintptr_t)pieces[g] + j * plen, plen, 0, 0}, h + 32 * j});
-            else if (j < k)  // share j of every stripe of the stripe-major segment
-                list.push_back({{(uint64_t)(uintptr_t)segs[g] + j * ess, plen, (uint64_t)ess, (int64_t)(k * ess)},
-                                h + 32 * j});
-            else
-                list.push_back({{(uint64_t)(uintptr_t)pieces[g] + (j - k) * plen, plen, 0, 0}, h + 32 * j});
-        }
-    }
+    if (int rc = segment_pieces(c, nseg, segs, nstripes, pieces, flags, hashes, list)) return rc;
     DeviceGuard dg(c->device);
-    return hash_list(c, list, hashes, hashes + 32 * n * nseg, (hipStream_t)stream);
+    return hash_list(c, list, hashes, hashes + 32 * (size_t)c->n * nseg, (hipStream_t)stream);
 }
 
 int ec_hash_list_stats(const ec_ctx *c, unsigned long long *fast, unsigned long long *bytewise,

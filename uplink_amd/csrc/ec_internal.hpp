@@ -474,6 +474,10 @@ struct ec_ctx {
     // launches of those two calls so far: fast chunk launches, byte chunk launches, parents
     // launches, oversize pieces sent through the uniform launch (ec_hash_list_stats)
     std::atomic<uint64_t> hl_fast{0}, hl_byte{0}, hl_parents{0}, hl_oversize{0};
+    // ec_sha256_pieces_list / ec_sha256_segments_sized (ec_sha256.cpp; staging from hash_sized too): blocks a
+    // launch advances a piece by (ec_sha256_set_launch_blocks; 0: shalist::kLaunchBlocks), and the pieces of
+    // either class and the launches so far (ec_sha256_list_stats)
+    std::atomic<uint64_t> sha_launch_blocks{0}, sha_fast{0}, sha_byte{0}, sha_launches{0};
     StagePool gcm_sized{256u << 10};  // staging of ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized (ec_gcm_sized.cpp)
     // cipher launches of those two calls so far, and their passes (ec_gcm_sized_stats)
     std::atomic<uint64_t> gs_seal{0}, gs_open{0}, gs_passes{0};

@@ -440,8 +440,8 @@ class SegmentCodec:
         pieces [nseg][n][nstripes*ess]   ([nseg][n-k][...] when parity_only)
     encode_segments_sized(segs, nstripes, pieces, data_len=None, parity_only=False, stream=None)
         segs, pieces   one buffer per segment, nstripes a sequence: a stripe count per segment
-    hash_segments_sized(segs, nstripes, pieces, hashes, parity_only=False, stream=None)
-        hashes [nseg][n][32]: the BLAKE3 hashes of that batch's pieces
+    hash_segments_sized(segs, nstripes, pieces, hashes, parity_only=False, stream=None, algo=None)
+        hashes [nseg][n][32]: the BLAKE3 (or, by algo, SHA-256) hashes of that batch's pieces
     rebuild_segments(nums, piece_ptrs, nstripes, out, nseg=1, piece_seg_stride=0,
                      out_seg_stride=0, stream=None)
         out    [nseg][nstripes][k][ess]
@@ -507,16 +507,18 @@ class SegmentCodec:
                                                 self._stream(stream))
         _raise(self.scheme.ctx, rc)
 
-    def hash_segments_sized(self, segs, nstripes, pieces, hashes, parity_only: bool = False, stream=None):
-        """The BLAKE3 hashes of all n pieces of every segment of an
-        encode_segments_sized batch (ec_hash_segments_sized;
+    def hash_segments_sized(self, segs, nstripes, pieces, hashes, parity_only: bool = False, stream=None, algo=None):
+        """The hashes of all n pieces of every segment of an
+        encode_segments_sized batch (ec_hash_segments_sized, or
+        ec_sha256_segments_sized for algo = PieceHashAlgorithm.SHA256;
         piecestore/upload.go:133,155,270), from the same segs / nstripes /
         pieces / parity_only, in one stream-ordered pass: hashes [nseg][n][32].
+        BLAKE3 unless `algo` says otherwise (hash.go:25).
         With parity_only the data pieces are read in place from the segments.
         nstripes[g] == 0 skips segment g.  Asynchronous on `stream`."""
         from . import piecehash
         piecehash.hash_segments_sized(self.scheme, segs, nstripes, pieces, hashes, parity_only=parity_only,
-                                      stream=stream)
+                                      stream=stream, algo=piecehash.DEFAULT_ALGORITHM if algo is None else algo)
 
     def decode_segments(self, nums: Iterable[int], piece_ptrs: Iterable[int], nstripes: int, out, nseg: int = 1,
                         piece_seg_stride: int = 0, out_seg_stride: int = 0, stream=None):

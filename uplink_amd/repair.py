@@ -12,7 +12,8 @@ segments in one stream-ordered pass.
   repair_segments      the regenerated pieces of a batch of segments (optionally
                        with every surplus share checked against the basis, flagged
                        segments corrected through Decode and repaired again; and
-                       the BLAKE3 piece hashes PutPiece sends, piecestore/upload.go:270)
+                       the piece hashes PutPiece sends, piecestore/upload.go:270:
+                       BLAKE3 or, by hash_algo, SHA-256)
   repair_segments_sized  the same for segments of different sizes in one call
                        (ec_repair_segments_sized): a repair queue holds segments of as
                        many sizes as there are objects
@@ -64,13 +65,15 @@ def repair_call(ctx, segments, out_ptrs: Sequence[int], nstripes: int, flags: in
         SegmentCodec._addr(status) if status is not None else None, SegmentCodec._stream(stream))
 
 
-def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, stream=None):
+def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, hash_algo=None,
+                    stream=None):
     """Regenerate the pieces `targets` of every segment of `segments`, each a
     (nums, pieces, targets): the piece numbers it still has, their device
     tensors (torch uint8, nstripes*ess bytes each, any order) and the piece
     numbers wanted.  Returns, per segment, a [len(targets), nstripes*ess] uint8
     device tensor whose row i is piece targets[i]; with hash_pieces, a pair of
-    that list and a list of [len(targets), 32] tensors of their BLAKE3 hashes.
+    that list and a list of [len(targets), 32] tensors of their hashes: BLAKE3,
+    or the algorithm hash_algo names (piecehash.PieceHashAlgorithm).
 
     check: every share beyond the k the repair is computed from is compared
     with them in the same pass.  A segment where one disagrees is corrected as
@@ -134,8 +137,9 @@ def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces
         if not hash_pieces:
             return outs
         # every regenerated row in one list call: they have one length and differ in where they lie
-        from .piecehash import blake3_pieces_list
-        flat = blake3_pieces_list(ctx, rows, stream=stream) if rows else None
+        from .piecehash import DEFAULT_ALGORITHM, hash_pieces_list
+        algo = DEFAULT_ALGORITHM if hash_algo is None else hash_algo
+        flat = hash_pieces_list(ctx, rows, stream=stream, algo=algo) if rows else None
         hashes, at = [], 0
         for o in outs:
             cnt = o.shape[0]
@@ -172,7 +176,8 @@ def _sizes_of(scheme_or_ctx, ctx):
     return lib.ec_share_size(ctx), lib.ec_required(ctx)
 
 
-def repair_segments_sized(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, stream=None):
+def repair_segments_sized(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, hash_algo=None,
+                          stream=None):
     """repair_segments for segments of different sizes, in one engine call
     (ec_repair_segments_sized): a repair queue holds segments of as many sizes
     as there are objects.  Each segment's piece length is that of its own
@@ -180,7 +185,8 @@ def repair_segments_sized(scheme_or_ctx, segments, *, check: bool = False, hash_
     length that is no multiple of the share size EC_ERR_INVALID_ARG, both
     raised before anything is queued.  Returns, per segment, its own
     [len(targets), piece_len] uint8 device tensor (with hash_pieces, also the
-    [len(targets), 32] hashes), each allocated on its own.
+    [len(targets), 32] hashes, by hash_algo as repair_segments), each allocated
+    on its own.
 
     check: as repair_segments; flagged segments are corrected through Decode
     with their own stripe count and repaired again in one sized call."""
@@ -240,8 +246,9 @@ def repair_segments_sized(scheme_or_ctx, segments, *, check: bool = False, hash_
         if not hash_pieces:
             return outs
         # every regenerated row of the batch in one list call, a length per piece
-        from .piecehash import blake3_pieces_list
-        flat = blake3_pieces_list(ctx, rows, stream=stream) if rows else None
+        from .piecehash import DEFAULT_ALGORITHM, hash_pieces_list
+        algo = DEFAULT_ALGORITHM if hash_algo is None else hash_algo
+        flat = hash_pieces_list(ctx, rows, stream=stream, algo=algo) if rows else None
         hashes, at = [], 0
         for o in outs:
             cnt = o.shape[0]
@@ -296,27 +303,27 @@ class SegmentRepairer:
         return [t for t in range(self.rs.total_count()) if t not in have]
 
     def repair(self, segments: Sequence[Dict[int, object]], *, check: bool = False, hash_pieces: bool = False,
-               stream=None):
+               hash_algo=None, stream=None):
         """segments: per segment a dict {piece number: device tensor} of its
         healthy pieces.  Returns per segment a dict {piece number: regenerated
         tensor} (empty where no repair is needed); with hash_pieces, also a dict
-        {piece number: 32-byte hash tensor} per segment."""
-        return self._repair(repair_segments, segments, check, hash_pieces, stream)
+        {piece number: 32-byte hash tensor} per segment (BLAKE3, or hash_algo's)."""
+        return self._repair(repair_segments, segments, check, hash_pieces, hash_algo, stream)
 
     def repair_sized(self, segments: Sequence[Dict[int, object]], *, check: bool = False, hash_pieces: bool = False,
-                     stream=None):
+                     hash_algo=None, stream=None):
         """repair for segments of different sizes (repair_segments_sized): each
         segment's pieces have the segment's own length."""
-        return self._repair(repair_segments_sized, segments, check, hash_pieces, stream)
+        return self._repair(repair_segments_sized, segments, check, hash_pieces, hash_algo, stream)
 
-    def _repair(self, call, segments, check, hash_pieces, stream):
+    def _repair(self, call, segments, check, hash_pieces, hash_algo, stream):
         batch, tg = [], []
         for seg in segments:
             nums = list(seg.keys())
             t = self.targets(nums)
             tg.append(t)
             batch.append((nums, [seg[x] for x in nums], t))
-        res = call(self.rs, batch, check=check, hash_pieces=hash_pieces, stream=stream)
+        res = call(self.rs, batch, check=check, hash_pieces=hash_pieces, hash_algo=hash_algo, stream=stream)
         outs, hashes = res if hash_pieces else (res, None)
         pieces = [{t: o[i] for i, t in enumerate(ts)} for ts, o in zip(tg, outs)]
         if not hash_pieces:

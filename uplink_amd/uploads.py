@@ -10,7 +10,8 @@ stream-ordered pass on the GPU.
 
   upload_geometry   (padded_size, piece_size, nstripes) of an upload
   encode_uploads    the pieces of a batch of uploads and, with hash_pieces, the
-                    BLAKE3 hash each piece is sent with (ec_hash_segments_sized)
+                    hash each piece is sent with (ec_hash_segments_sized; SHA-256 by
+                    hash_algo: ec_sha256_segments_sized)
   cipher_geometry   (nblocks, plain_cap, enc_len) of an upload through the cipher
   seal_uploads      the encrypted segments of a batch of uploads, each in the
                     buffer encode_uploads takes (ec_gcm_seal_segments_sized)
@@ -35,18 +36,19 @@ def upload_geometry(size: int, es) -> Tuple[int, int, int]:
 
 
 def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only: bool = False,
-                   hash_pieces: bool = False, stream=None):
+                   hash_pieces: bool = False, hash_algo=None, stream=None):
     """uploads: per upload (size, buffer); `buffer` is a uint8 device tensor of
     at least padded_size bytes (upload_geometry) whose first `size` bytes are
     the data.  Its tail is overwritten with PadReader's padding.  Returns per
     upload a [n, piece_size] device tensor of its pieces ([n-k, piece_size] with
     parity_only).  A buffer that is too short raises before anything is queued.
     With hash_pieces it returns (pieces, hashes): hashes[g] is the [n, 32]
-    device tensor of the BLAKE3 hashes upload g's pieces are sent with
-    (piecestore/upload.go:270), all n rows also with parity_only (the data
+    device tensor of the hashes upload g's pieces are sent with
+    (piecestore/upload.go:270) -- BLAKE3, or the algorithm hash_algo names
+    (piecehash.PieceHashAlgorithm; WithPieceHashAlgo) --, all n rows also with parity_only (the data
     pieces are then hashed in place from the padded buffer); the rows are views
-    of one buffer, filled by one ec_hash_segments_sized call queued behind the
-    encode.  Asynchronous on `stream`."""
+    of one buffer, filled by one ec_hash_segments_sized (ec_sha256_segments_sized)
+    call queued behind the encode.  Asynchronous on `stream`."""
     import torch
 
     codec = SegmentCodec(scheme)
@@ -70,7 +72,7 @@ def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only
         dev = geo[0][3].device if geo else "cuda"
         hashes = torch.empty((len(geo), scheme.total_count(), 32), dtype=torch.uint8, device=dev)
         codec.hash_segments_sized([g[3] for g in geo], [g[2] for g in geo], outs, hashes, parity_only=parity_only,
-                                  stream=stream)
+                                  stream=stream, algo=hash_algo)
     return outs, [hashes[g] for g in range(len(geo))]
 
 
