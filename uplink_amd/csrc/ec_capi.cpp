@@ -444,28 +444,6 @@ int run_matmul(ec_ctx *c, RsArgs a, const int64_t *out_off, MatPlan &plan, int64
     return EC_OK;
 }
 
-// infectious Rebuild share choice: sort by number, then for i in 0..k-1 take
-// the front share if its number == i else take from the back.
-int choose_shares(const ec_ctx *c, int nshares, const int *nums, std::vector<int> &order_out,
-                  std::vector<int> &ids_out) {
-    if (nshares < c->k) return EC_ERR_NOT_ENOUGH_SHARES;
-    std::vector<int> order(nshares);
-    for (int i = 0; i < nshares; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nums[a] < nums[b]; });
-    int b = 0, e = nshares - 1;
-    order_out.clear();
-    ids_out.clear();
-    for (int i = 0; i < c->k; i++) {
-        int pick;
-        if (nums[order[b]] == i) pick = order[b++];
-        else pick = order[e--];
-        if (nums[pick] >= c->n || nums[pick] < 0) return EC_ERR_INVALID_SHARE;
-        order_out.push_back(pick);
-        ids_out.push_back(nums[pick]);
-    }
-    return EC_OK;
-}
-
 // Decode plan for the chosen ids (one inversion per share set).
 int get_plan(ec_ctx *c, const std::vector<int> &ids, PlanPtr *out) {
     return cached_plan(c, ids, [&](std::vector<uint8_t> &M, int &rows, std::vector<int> &missing) {

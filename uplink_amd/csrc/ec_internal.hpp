@@ -27,6 +27,7 @@
 #include "rs_repair.hpp"
 #include "rs_sets.hpp"
 #include "rs_sl.hpp"
+#include "share_pick.hpp"
 
 
 #pragma GCC visibility push(hidden)  // (internal to the library: not in its dynamic symbol table)
@@ -507,10 +508,10 @@ constexpr int64_t kJitMinTiles = 256;
 int hip_fail(hipError_t e);
 bool aligned16(const void *p);
 int after_launch(uint32_t *chk, hipStream_t s);
-// infectious Rebuild share choice: sort by number, then for i in 0..k-1 take
-// the front share if its number == i else take from the back.
-int choose_shares(const ec_ctx *c, int nshares, const int *nums, std::vector<int> &order_out,
-                  std::vector<int> &ids_out);
+// infectious Rebuild share choice for the context's code (share_pick.hpp)
+inline int choose_shares(const ec_ctx *c, int nshares, const int *nums, std::vector<int> &order, std::vector<int> &ids) {
+    return uplink_ec::choose_shares(c->k, c->n, nshares, nums, order, ids);
+}
 int get_plan(ec_ctx *c, const std::vector<int> &ids, PlanPtr *out);
 // cached plan of the rows x nin matrix M under `key` (repair's byte path: keys that start with -5)
 int matrix_plan(ec_ctx *c, const std::vector<int> &key, const uint8_t *M, int rows, int nin, PlanPtr *out);

@@ -4,8 +4,7 @@
 // straight from the k basis shares in one stream-ordered pass (rs_repair.hpp).
 // The host chooses the basis as Rebuild does, solves each segment's rows in
 // closed form (LagrangeBasis) and stages them; nothing waits for the stream.
-#include "ec_internal.hpp"
-#include "sized_geom.hpp"
+#include "ec_stage_pass.hpp"
 
 namespace uplink_ec {
 namespace capi {
@@ -18,7 +17,7 @@ struct RepairSeg {
     std::vector<int> tnum;            // targets
     std::vector<uint8_t *> out;
     size_t g = 0;                     // segment of the call
-    int64_t nstripes = 0, chunks = 0, tiles = 0;  // the sized call: the segment's own geometry
+    int64_t nstripes = 0, chunks = 0, tiles = 0;  // its geometry (the sized call: its own)
     int rows = 0, nw = 2;
     bool bits = true;
 };
@@ -42,30 +41,13 @@ int prepare_segment(const ec_ctx *c, bool check, int ns, const int *snum, const 
         if (given[tnum[r]] || wanted[tnum[r]] || !op[r]) return EC_ERR_INVALID_ARG;
         wanted[tnum[r]] = true;
     }
-    std::vector<int> order, ids;
-    if (int rc = choose_shares(c, ns, snum, order, ids)) return rc;
-    bool seen[256] = {};
-    std::vector<char> chosen(ns, 0);
-    for (int i = 0; i < k; i++) {
-        if (seen[ids[i]]) return EC_ERR_SINGULAR;
-        seen[ids[i]] = true;
-        chosen[order[i]] = 1;
-        sg.in.push_back(sp[order[i]]);
-        sg.num.push_back(ids[i]);
-    }
-    if (check) {  // the other shares, by number (as the share-set decode orders them)
-        std::vector<int> rest;
-        for (int i = 0; i < ns; i++)
-            if (!chosen[i]) rest.push_back(i);
-        std::stable_sort(rest.begin(), rest.end(), [&](int x, int y) { return snum[x] < snum[y]; });
-        for (int i : rest) {
-            sg.in.push_back(sp[i]);
-            sg.num.push_back(snum[i]);
-        }
-    }
+    int pos[kMaxOps], nin, nparity;
+    sg.num.resize(check ? ns : k);
+    if (int rc = pick_inputs(k, n, ns, snum, false, check, pos, sg.num.data(), nullptr, nin, nparity)) return rc;
+    for (int j = 0; j < nin; j++) sg.in.push_back(sp[pos[j]]);
     sg.tnum.assign(tnum, tnum + nt);
     sg.out.assign(op, op + nt);
-    sg.rows = nt + (int)sg.in.size() - k;
+    sg.rows = nt + nin - k;
     sg.nw = repair_waves(sg.rows);
     sg.bits = ess % 16 == 0;
     for (const uint8_t *p : sg.in) sg.bits = sg.bits && aligned16(p);
@@ -126,77 +108,44 @@ int repair_bytes(ec_ctx *c, const RepairSeg &sg, int64_t nstripes, int32_t *stat
     return EC_OK;
 }
 
-int repair_call(ec_ctx *c, std::vector<RepairSeg> &segs, int64_t nstripes, int32_t *dev_status, bool check,
-                hipStream_t s) {
-    const int k = c->k, ess = c->ess;
-    const int64_t piece_len = nstripes * ess;
-    std::vector<int> idx;  // the bit-sliced kernel's segments, by wave-count class
-    for (size_t i = 0; i < segs.size(); i++)
-        if (segs[i].bits) idx.push_back((int)i);
-    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return segs[x].nw < segs[y].nw; });
-    const size_t nb = idx.size();
-    for (auto &sg : segs)
-        if (!sg.bits)
-            if (int rc = repair_bytes(c, sg, nstripes, check ? dev_status + sg.g : nullptr, s)) return rc;
-    if (nb == 0) return EC_OK;
-    std::vector<size_t> eoff(nb + 1, 0);
-    for (size_t q = 0; q < nb; q++) {
-        const RepairSeg &sg = segs[idx[q]];
-        eoff[q + 1] = eoff[q] + staged_entries((int)sg.in.size(), sg.rows, sg.nw);
-    }
-    const size_t h_stage = nb * sizeof(RepairStage), d_desc = up(nb * sizeof(RepairDesc), 256);
-    StageBlock *b = block_acquire(c->repair, h_stage + eoff[nb], d_desc + eoff[nb] * 8);
-    if (!b) return EC_ERR_DEVICE;
-    RepairStage *stage = (RepairStage *)b->h;
-    uint8_t *h_coef = b->h + h_stage;
-    RepairDesc *d_descs = (RepairDesc *)b->d;
-    uint64_t *d_tgt = (uint64_t *)(b->d + d_desc);
-    std::vector<uint8_t> M;
-    for (size_t q = 0; q < nb; q++) {
-        const RepairSeg &sg = segs[idx[q]];
-        const int nin = (int)sg.in.size(), nt = (int)sg.tnum.size(), nw = sg.nw;
-        RepairStage &st = stage[q];
-        memset(&st, 0, sizeof(st));
-        for (int j = 0; j < nin; j++) st.d.in[j] = sg.in[j];
-        for (int r = 0; r < nt; r++) st.d.out[r] = sg.out[r];
-        st.d.tgt = d_tgt + eoff[q];
+// The fields only a repair descriptor has (RepairDesc and RepairSizedDesc alike).
+auto repair_fields(int32_t *dev_status, bool check) {
+    return [=](auto &st, const RepairSeg &sg, size_t, const auto &) {
+        for (size_t r = 0; r < sg.out.size(); r++) st.d.out[r] = sg.out[r];
         st.d.status = check ? dev_status + sg.g : nullptr;
-        st.d.nin = nin;
-        st.d.nout = sg.rows;
-        st.d.nstore = nt;
-        st.d.nw = nw;
-        st.coef = h_coef + eoff[q];
-        st.entries = (int64_t)(eoff[q + 1] - eoff[q]);
-        // the rows (targets, then the syndrome rows) in the leaf table's order
-        M.resize((size_t)sg.rows * nin);
-        solve_rows(sg.num.data(), k, nin, sg.tnum.data(), nt, M.data());
-        pack_rows(M.data(), sg.rows, nin, nw, h_coef + eoff[q]);
-    }
-    hipError_t e = launch_repair_prep(stage, d_descs, (int)nb, c->jt_base, s);
-    if (e != hipSuccess) {  // nothing was queued
-        block_release(c->repair, b, false, s);
-        return hip_fail(e);
-    }
-    const int64_t chunks = piece_len / 16, tiles = (chunks + kTileChunksHost - 1) / kTileChunksHost;
-    for (size_t q0 = 0; q0 < nb && e == hipSuccess;) {
-        const int nw = segs[idx[q0]].nw;
-        size_t q1 = q0;
-        // (more tiles than one launch takes: in parts)
-        while (q1 < nb && segs[idx[q1]].nw == nw && (int64_t)(q1 + 1 - q0) * tiles <= share_max_tiles(nw)) q1++;
-        RepairArgs a{};
-        a.desc = d_descs + q0;
-        a.piece_len = piece_len;
-        a.chunks_per_seg = chunks;
-        a.tiles_per_seg = tiles;
-        a.total_tiles = tiles * (int64_t)(q1 - q0);
-        a.chk_flag = c->d_chk;
-        e = launch_repair(a, nw, s);
-        q0 = q1;
-    }
-    block_release(c->repair, b, true, s);
-    if (e != hipSuccess) return hip_fail(e);
-    c->last_body = EC_BODY_JUMP_TABLE;
-    return after_launch(c->d_chk, s);
+        st.d.nw = sg.nw;
+    };
+}
+
+// The pass of ec_repair_segments_sets over segs[0..n), all of one size:
+// rs_repair_prep, then the tile kernel per wave-count class over whole segments
+// (a class of more tiles than one launch takes in parts), all on stream s.
+int repair_call(ec_ctx *c, RepairSeg **segs, size_t n, int32_t *dev_status, bool check, hipStream_t s) {
+    std::stable_sort(segs, segs + n, [](const RepairSeg *x, const RepairSeg *y) { return x->nw < y->nw; });
+    return staged_pass<RepairStage>(
+        c, c->repair, n, [&](size_t q) -> const RepairSeg & { return *segs[q]; }, &RepairSeg::tnum, nullptr, 0,
+        repair_fields(dev_status, check), launch_repair_prep,
+        [&](const StagedPass<RepairStage> &p) {
+            const int64_t chunks = segs[0]->chunks, tiles = segs[0]->tiles;
+            hipError_t e = hipSuccess;
+            for (size_t q0 = 0; q0 < n && e == hipSuccess;) {
+                const int nw = segs[q0]->nw;
+                size_t q1 = q0;
+                // (more tiles than one launch takes: in parts)
+                while (q1 < n && segs[q1]->nw == nw && (int64_t)(q1 + 1 - q0) * tiles <= share_max_tiles(nw)) q1++;
+                RepairArgs a{};
+                a.desc = p.desc + q0;
+                a.piece_len = chunks * 16;
+                a.chunks_per_seg = chunks;
+                a.tiles_per_seg = tiles;
+                a.total_tiles = tiles * (int64_t)(q1 - q0);
+                a.chk_flag = c->d_chk;
+                e = launch_repair(a, nw, s);
+                q0 = q1;
+            }
+            return e;
+        },
+        s);
 }
 
 // One pass of a sized call over segs[0..n), segments of their own sizes:
@@ -204,7 +153,6 @@ int repair_call(ec_ctx *c, std::vector<RepairSeg> &segs, int64_t nstripes, int32
 // a class has more tiles than a launch takes), all on stream s; staged as
 // repair_call stages, plus the classes' tile maps (sized_geom.hpp).
 int repair_sized_pass(ec_ctx *c, RepairSeg *const *segs, size_t n, int32_t *dev_status, bool check, hipStream_t s) {
-    const int k = c->k;
     std::vector<int> nw(n);
     std::vector<int64_t> tiles(n);
     for (size_t i = 0; i < n; i++) {
@@ -212,125 +160,37 @@ int repair_sized_pass(ec_ctx *c, RepairSeg *const *segs, size_t n, int32_t *dev_
         tiles[i] = segs[i]->tiles;
     }
     const sized::Layout L = sized::layout(nw.data(), tiles.data(), n, share_max_tiles);
-    std::vector<size_t> eoff(n + 1, 0);
-    for (size_t q = 0; q < n; q++) {
-        const RepairSeg &sg = *segs[L.idx[q]];
-        eoff[q + 1] = eoff[q] + staged_entries((int)sg.in.size(), sg.rows, sg.nw);
-    }
-    const size_t h_stage = up(n * sizeof(RepairSizedStage), 16);
-    const size_t d_desc = up(n * sizeof(RepairSizedDesc), 256), d_tgt_len = eoff[n] * 8;
-    StageBlock *b = block_acquire(c->repair, h_stage + eoff[n], d_desc + d_tgt_len + (size_t)L.map_entries * 4);
-    if (!b) return EC_ERR_DEVICE;
-    RepairSizedStage *stage = (RepairSizedStage *)b->h;
-    uint8_t *h_coef = b->h + h_stage;
-    RepairSizedDesc *d_descs = (RepairSizedDesc *)b->d;
-    uint64_t *d_tgt = (uint64_t *)(b->d + d_desc);
-    uint32_t *d_map = (uint32_t *)(b->d + d_desc + d_tgt_len);
-    std::vector<uint8_t> M;
-    for (size_t q = 0; q < n; q++) {
-        const RepairSeg &sg = *segs[L.idx[q]];
-        const int nin = (int)sg.in.size(), nt = (int)sg.tnum.size();
-        RepairSizedStage &st = stage[q];
-        memset(&st, 0, sizeof(st));
-        for (int j = 0; j < nin; j++) st.d.in[j] = sg.in[j];
-        for (int r = 0; r < nt; r++) st.d.out[r] = sg.out[r];
-        st.d.tgt = d_tgt + eoff[q];
-        st.d.status = check ? dev_status + sg.g : nullptr;
-        st.d.nin = nin;
-        st.d.nout = sg.rows;
-        st.d.nstore = nt;
-        st.d.nw = sg.nw;
-        st.d.chunks = sg.chunks;
-        st.d.piece_len = sg.chunks * 16;
-        st.d.tile0 = L.tile0[q];
-        st.coef = h_coef + eoff[q];
-        st.entries = (int64_t)(eoff[q + 1] - eoff[q]);
-        st.map = d_map + L.map_off[q] + L.tile0[q];
-        st.ntiles = sg.tiles;
-        // the rows (targets, then the syndrome rows) in the leaf table's order
-        M.resize((size_t)sg.rows * nin);
-        solve_rows(sg.num.data(), k, nin, sg.tnum.data(), nt, M.data());
-        pack_rows(M.data(), sg.rows, nin, sg.nw, h_coef + eoff[q]);
-    }
-    hipError_t e = launch_repair_sized_prep(stage, d_descs, (int)n, c->jt_base, s);
-    if (e != hipSuccess) {  // nothing was queued
-        block_release(c->repair, b, false, s);
-        return hip_fail(e);
-    }
-    for (const sized::Launch &ln : L.launches) {
-        RepairSizedArgs a{};
-        a.desc = d_descs;
-        a.map = d_map + ln.map_off;
-        a.tile_base = ln.tile_base;
-        a.total_tiles = ln.tiles;
-        a.chk_flag = c->d_chk;
-        e = launch_repair_sized(a, ln.nw, s);
-        if (e != hipSuccess) break;
-    }
-    block_release(c->repair, b, true, s);
-    if (e != hipSuccess) return hip_fail(e);
-    c->last_body = EC_BODY_JUMP_TABLE;
-    return after_launch(c->d_chk, s);
+    return staged_pass<RepairSizedStage>(
+        c, c->repair, n, [&](size_t q) -> const RepairSeg & { return *segs[L.idx[q]]; }, &RepairSeg::tnum, &L, 0,
+        repair_fields(dev_status, check), launch_repair_sized_prep,
+        [&](const StagedPass<RepairSizedStage> &p) {
+            hipError_t e = hipSuccess;
+            for (size_t i = 0; i < L.launches.size() && e == hipSuccess; i++) {
+                const sized::Launch &ln = L.launches[i];
+                RepairSizedArgs a{};
+                a.desc = p.desc;
+                a.map = p.map + ln.map_off;
+                a.tile_base = ln.tile_base;
+                a.total_tiles = ln.tiles;
+                a.chk_flag = c->d_chk;
+                e = launch_repair_sized(a, ln.nw, s);
+            }
+            return e;
+        },
+        s);
 }
 
-}  // namespace
-}  // namespace capi
-}  // namespace uplink_ec
-
-extern "C" {
-
-int ec_repair_segments_sets(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums,
-                            const uint8_t *const *pieces, const int *ntargets, const int *targets,
-                            uint8_t *const *outs, size_t nstripes, int flags, int32_t *dev_status, ec_stream stream) {
+// Both exports: segment g has nstripes_of[g] stripes, or -- nstripes_of null --
+// every segment has `nstripes`.
+int repair_export(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums, const uint8_t *const *pieces,
+                  const int *ntargets, const int *targets, uint8_t *const *outs, const size_t *nstripes_of,
+                  size_t nstripes, int flags, int32_t *dev_status, ec_stream stream) {
     ec_ctx *c = const_cast<ec_ctx *>(cc);
     if (!c || (nseg && (!nshares || !nums || !pieces || !ntargets || !targets || !outs))) return EC_ERR_INVALID_ARG;
     if (flags & ~EC_FLAG_CHECK_SHARES) return EC_ERR_INVALID_ARG;
     const bool check = (flags & EC_FLAG_CHECK_SHARES) != 0;
     if (check && !dev_status) return EC_ERR_INVALID_ARG;
-    if (nseg == 0 || nstripes == 0) return EC_OK;
-    const int k = c->k, ess = c->ess;
-    if (k > kMaxOps) return EC_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    // every segment is validated before anything is queued
-    std::vector<RepairSeg> segs;
-    size_t soff = 0, toff = 0;
-    for (size_t g = 0; g < nseg; g++) {
-        const int ns = nshares[g], nt = ntargets[g];
-        if (nt < 0) return EC_ERR_INVALID_ARG;
-        const int *snum = nums + soff, *tnum = targets + toff;
-        const uint8_t *const *sp = pieces + soff;
-        uint8_t *const *op = outs + toff;
-        soff += (size_t)std::max(ns, 0);
-        toff += (size_t)nt;
-        if (nt == 0) continue;
-        RepairSeg sg;
-        if (int rc = prepare_segment(c, check, ns, snum, sp, nt, tnum, op, sg)) return rc;
-        sg.g = g;
-        if (sg.bits) {
-            const int64_t tiles = ((int64_t)nstripes * (ess / 16) + kTileChunksHost - 1) / kTileChunksHost;
-            if (tiles > share_max_tiles(sg.nw)) return EC_ERR_UNSUPPORTED;
-        }
-        segs.push_back(std::move(sg));
-    }
-    DeviceGuard dg(c->device);
-    // staging blocks are recycled by events behind launches that run: not under stream capture
-    if (stream_is_capturing(s)) return EC_ERR_UNSUPPORTED;
-    if (check) HIP_TRY(hipMemsetAsync(dev_status, 0, sizeof(int32_t) * nseg, s));
-    if (segs.empty()) return EC_OK;
-    return repair_call(c, segs, (int64_t)nstripes, dev_status, check, s);
-}
-
-int ec_repair_segments_sized(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums,
-                             const uint8_t *const *pieces, const int *ntargets, const int *targets,
-                             uint8_t *const *outs, const size_t *nstripes, int flags, int32_t *dev_status,
-                             ec_stream stream) {
-    ec_ctx *c = const_cast<ec_ctx *>(cc);
-    if (!c || (nseg && (!nshares || !nums || !pieces || !ntargets || !targets || !outs || !nstripes)))
-        return EC_ERR_INVALID_ARG;
-    if (flags & ~EC_FLAG_CHECK_SHARES) return EC_ERR_INVALID_ARG;
-    const bool check = (flags & EC_FLAG_CHECK_SHARES) != 0;
-    if (check && !dev_status) return EC_ERR_INVALID_ARG;
-    if (nseg == 0) return EC_OK;
+    if (nseg == 0 || (!nstripes_of && nstripes == 0)) return EC_OK;
     const int ess = c->ess;
     if (c->k > kMaxOps) return EC_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
@@ -345,14 +205,17 @@ int ec_repair_segments_sized(const ec_ctx *cc, size_t nseg, const int *nshares, 
         uint8_t *const *op = outs + toff;
         soff += (size_t)std::max(ns, 0);
         toff += (size_t)nt;
-        if (nt == 0 || nstripes[g] == 0) continue;
+        const size_t stripes = nstripes_of ? nstripes_of[g] : nstripes;
+        if (nt == 0 || stripes == 0) continue;
         RepairSeg sg;
         if (int rc = prepare_segment(c, check, ns, snum, sp, nt, tnum, op, sg)) return rc;
         sg.g = g;
-        sg.chunks = sized::chunks_of(nstripes[g], ess);
+        sg.nstripes = (int64_t)stripes;
+        // (one size for all: only what the one launch per class cannot take is refused, below)
+        sg.chunks = nstripes_of ? sized::chunks_of(stripes, ess) : sg.nstripes * (ess / 16);
         if (sg.chunks < 0) return EC_ERR_UNSUPPORTED;
-        sg.nstripes = (int64_t)nstripes[g];
         sg.tiles = sized::tiles_of(sg.chunks);
+        if (!nstripes_of && sg.bits && sg.tiles > share_max_tiles(sg.nw)) return EC_ERR_UNSUPPORTED;
         segs.push_back(std::move(sg));
     }
     DeviceGuard dg(c->device);
@@ -368,11 +231,34 @@ int ec_repair_segments_sized(const ec_ctx *cc, size_t nseg, const int *nshares, 
         }
         if (int rc = repair_bytes(c, sg, sg.nstripes, check ? dev_status + sg.g : nullptr, s)) return rc;
     }
+    if (!nstripes_of) return list.empty() ? EC_OK : repair_call(c, list.data(), list.size(), dev_status, check, s);
     std::vector<int64_t> tiles(list.size());
     for (size_t i = 0; i < list.size(); i++) tiles[i] = list[i]->tiles;
     for (const sized::Pass &p : sized::split_passes(tiles.data(), list.size(), sized::kPassSegs, sized::kPassTiles))
         if (int rc = repair_sized_pass(c, list.data() + p.i0, p.i1 - p.i0, dev_status, check, s)) return rc;
     return EC_OK;
+}
+
+}  // namespace
+}  // namespace capi
+}  // namespace uplink_ec
+
+extern "C" {
+
+int ec_repair_segments_sets(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums,
+                            const uint8_t *const *pieces, const int *ntargets, const int *targets,
+                            uint8_t *const *outs, size_t nstripes, int flags, int32_t *dev_status, ec_stream stream) {
+    return repair_export(cc, nseg, nshares, nums, pieces, ntargets, targets, outs, nullptr, nstripes, flags, dev_status,
+                         stream);
+}
+
+int ec_repair_segments_sized(const ec_ctx *cc, size_t nseg, const int *nshares, const int *nums,
+                             const uint8_t *const *pieces, const int *ntargets, const int *targets,
+                             uint8_t *const *outs, const size_t *nstripes, int flags, int32_t *dev_status,
+                             ec_stream stream) {
+    if (nseg && !nstripes) return EC_ERR_INVALID_ARG;
+    return repair_export(cc, nseg, nshares, nums, pieces, ntargets, targets, outs, nstripes, 0, flags, dev_status,
+                         stream);
 }
 
 }  // extern "C"

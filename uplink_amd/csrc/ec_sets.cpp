@@ -4,6 +4,7 @@
 // stream-ordered pass (rs_sets.hpp), and the per-context background builder
 // of decode plans' straight-line code.
 #include "ec_internal.hpp"
+#include "sized_geom.hpp"
 
 namespace uplink_ec {
 namespace capi {
@@ -28,37 +29,13 @@ struct SetSeg {
 // share chosen twice: singular).
 int set_segment(const ec_ctx *c, int nshares, const int *nums, const uint8_t *const *pieces, uint8_t *out,
                 bool decode, SetSeg &sg) {
-    const int k = c->k;
-    std::vector<int> order, ids;
-    int rc = choose_shares(c, nshares, nums, order, ids);
-    if (rc) return rc;
-    if (decode)
-        for (int i = 0; i < nshares; i++)
-            if (nums[i] < 0 || nums[i] >= c->n) return EC_ERR_INVALID_SHARE;
-    bool seen[256] = {};
-    sg.nin = k;
-    sg.nstore = 0;
-    for (int i = 0; i < k; i++) {
-        if (seen[ids[i]]) return EC_ERR_SINGULAR;
-        seen[ids[i]] = true;
-        sg.in[i] = pieces[order[i]];
-        sg.num[i] = ids[i];
-        if (ids[i] >= k) sg.missing[sg.nstore++] = i;
-    }
-    if (decode) {
-        if (nshares > kMaxOps) return EC_ERR_UNSUPPORTED;
-        std::vector<char> chosen(nshares, 0);
-        for (int i = 0; i < k; i++) chosen[order[i]] = 1;
-        std::vector<int> rest;
-        for (int i = 0; i < nshares; i++)
-            if (!chosen[i]) rest.push_back(i);
-        std::stable_sort(rest.begin(), rest.end(), [&](int x, int y) { return nums[x] < nums[y]; });
-        for (int i : rest) {
-            sg.in[sg.nin] = pieces[i];
-            sg.num[sg.nin++] = nums[i];
-        }
-    }
-    sg.rows = sg.nstore + (sg.nin - k);
+    int pos[kMaxOps];
+    if (int rc = pick_inputs(c->k, c->n, nshares, nums, decode, decode && nshares <= kMaxOps, pos, sg.num, sg.missing,
+                             sg.nin, sg.nstore))
+        return rc;
+    if (decode && nshares > kMaxOps) return EC_ERR_UNSUPPORTED;
+    for (int j = 0; j < sg.nin; j++) sg.in[j] = pieces[pos[j]];
+    sg.rows = sg.nstore + (sg.nin - c->k);
     sg.nw = sets_waves(sg.rows);
     sg.out = out;
     return EC_OK;
@@ -163,8 +140,7 @@ int sets_call(ec_ctx *c, std::vector<SetSeg> &segs, int64_t nstripes, hipStream_
         for (auto &sg : segs) sg.nw = nw;
     }
     {  // more tiles than one launch takes: in parts (each a call of its own)
-        const int64_t tiles_seg = (nstripes * (ess / 16) + kTileChunksHost - 1) / kTileChunksHost;
-        const int64_t per = share_max_tiles(4) / tiles_seg;
+        const int64_t per = share_max_tiles(4) / sized::tiles_of(nstripes * (ess / 16));
         if (per < 1) return EC_ERR_UNSUPPORTED;
         if ((int64_t)nseg > per) {
             for (size_t g0 = 0; g0 < nseg; g0 += (size_t)per) {
@@ -218,7 +194,7 @@ int sets_call(ec_ctx *c, std::vector<SetSeg> &segs, int64_t nstripes, hipStream_
         st.nw = sg.nw;
     }
     const uint32_t seq = sl->seq + 1;
-    const int64_t chunks = nstripes * (ess / 16), tiles = (chunks + kTileChunksHost - 1) / kTileChunksHost;
+    const int64_t chunks = nstripes * (ess / 16), tiles = sized::tiles_of(chunks);
     // a pass's arguments, but for its segments (desc, total_tiles)
     auto pass_args = [&](SetsArgs &a) {
         a.nstripes = nstripes;
@@ -422,7 +398,7 @@ int rebuild_async(ec_ctx *c, int nshares, const int *nums, const uint8_t *const 
     // kernel; its plan has no tables to wait for): the plan path
     if (!bits || m == 0 || c->body == EC_BODY_STRAIGHT_LINE)
         return rebuild_device(c, nshares, nums, pieces, ess, nstripes, nseg, pss, oss, out, s);
-    const int64_t tiles = (nstripes * (ess / 16) + kTileChunksHost - 1) / kTileChunksHost * nseg;
+    const int64_t tiles = sized::tiles_of(nstripes * (ess / 16)) * nseg;
     if (c->body == EC_BODY_AUTO && tiles >= kSlMinTiles) {
         if (PlanPtr plan = find_plan(c, ids); plan && plan->sl_ready.load(std::memory_order_acquire))
             return rebuild_with_plan(c, *plan, order, ids, pieces, ess, nstripes, nseg, pss, oss, out, s);

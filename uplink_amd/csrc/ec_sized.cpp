@@ -6,9 +6,8 @@
 // stages them with the geometry (sized_geom.hpp) in event-recycled blocks, as
 // segment repair does (ec_repair.cpp); nothing on the Rebuild path waits for
 // the stream.
-#include "ec_internal.hpp"
+#include "ec_stage_pass.hpp"
 #include "rs_sized.hpp"
-#include "sized_geom.hpp"
 
 namespace uplink_ec {
 namespace capi {
@@ -35,33 +34,16 @@ struct SizedSeg {
 int prepare_segment(const ec_ctx *c, int nshares, const int *nums, const uint8_t *const *pieces, bool decode,
                     SizedSeg &sg) {
     const int k = c->k;
-    if (decode)
-        for (int i = 0; i < nshares; i++)
-            if (nums[i] < 0 || nums[i] >= c->n) return EC_ERR_INVALID_SHARE;
-    std::vector<int> order, ids;
-    if (int rc = choose_shares(c, nshares, nums, order, ids)) return rc;
-    bool seen[256] = {};
-    std::vector<char> chosen(nshares, 0);
-    for (int i = 0; i < k; i++) {
-        if (seen[ids[i]]) return EC_ERR_SINGULAR;
-        seen[ids[i]] = true;
-        chosen[order[i]] = 1;
-        sg.in.push_back(pieces[order[i]]);
-        sg.num.push_back(ids[i]);
-        if (ids[i] >= k) sg.missing.push_back(i);
-    }
     sg.own = decode && nshares > kMaxOps;
-    if (decode && !sg.own) {  // the other shares, by number (as the share-set decode orders them)
-        std::vector<int> rest;
-        for (int i = 0; i < nshares; i++)
-            if (!chosen[i]) rest.push_back(i);
-        std::stable_sort(rest.begin(), rest.end(), [&](int x, int y) { return nums[x] < nums[y]; });
-        for (int i : rest) {
-            sg.in.push_back(pieces[i]);
-            sg.num.push_back(nums[i]);
-        }
-    }
-    sg.rows = (int)sg.missing.size() + (int)sg.in.size() - k;
+    const bool rest = decode && !sg.own;  // the other shares too, by number (as the share-set decode orders them)
+    int pos[kMaxOps], nin, nst;
+    sg.num.resize(rest ? nshares : k);
+    sg.missing.resize(k);
+    if (int rc = pick_inputs(k, c->n, nshares, nums, decode, rest, pos, sg.num.data(), sg.missing.data(), nin, nst))
+        return rc;
+    sg.missing.resize(nst);
+    for (int j = 0; j < nin; j++) sg.in.push_back(pieces[pos[j]]);
+    sg.rows = nst + nin - k;
     sg.nw = sets_waves(sg.rows);
     return EC_OK;
 }
@@ -82,82 +64,46 @@ int sized_pass(ec_ctx *c, SizedSeg *const *segs, size_t n, hipStream_t s, std::v
         tiles[i] = segs[i]->tiles;
     }
     const sized::Layout L = sized::layout(nw.data(), tiles.data(), n, share_max_tiles);
-    std::vector<size_t> eoff(n + 1, 0);
-    for (size_t q = 0; q < n; q++) {
-        const SizedSeg &sg = *segs[L.idx[q]];
-        eoff[q + 1] = eoff[q] + staged_entries((int)sg.in.size(), sg.rows, sg.nw);
-    }
-    const size_t h_stage = up(n * sizeof(SizedStage), 16), h_coef_len = eoff[n];
-    const size_t d_desc = up(n * sizeof(SizedDesc), 256), d_tgt_len = eoff[n] * 8;
-    const size_t d_map_len = up((size_t)L.map_entries * 4, 256);
-    StageBlock *b = block_acquire(c->sized, h_stage + h_coef_len + n * 4, d_desc + d_tgt_len + d_map_len + n * 4);
-    if (!b) return EC_ERR_DEVICE;
-    SizedStage *stage = (SizedStage *)b->h;
-    uint8_t *h_coef = b->h + h_stage;
-    uint32_t *h_cnt = (uint32_t *)(b->h + h_stage + h_coef_len);
-    SizedDesc *d_descs = (SizedDesc *)b->d;
-    uint64_t *d_tgt = (uint64_t *)(b->d + d_desc);
-    uint32_t *d_map = (uint32_t *)(b->d + d_desc + d_tgt_len);
-    uint32_t *d_cnt = (uint32_t *)(b->d + d_desc + d_tgt_len + d_map_len);
-    std::vector<uint8_t> M;
-    for (size_t q = 0; q < n; q++) {
-        const SizedSeg &sg = *segs[L.idx[q]];
-        const int nin = (int)sg.in.size(), nst = (int)sg.missing.size(), w = sg.nw;
-        SizedStage &st = stage[q];
-        memset(&st, 0, sizeof(st));
-        for (int j = 0; j < nin; j++) {
-            st.d.in[j] = sg.in[j];
-            st.d.copy_off[j] = j < k && sg.num[j] < k ? sg.num[j] * ess : -1;
-        }
-        for (int r = 0; r < nst; r++) st.d.out_off[r] = sg.missing[r] * ess;
-        st.d.out = sg.out;
-        st.d.tgt = d_tgt + eoff[q];
-        st.d.zero_check = bad ? d_cnt + q : nullptr;
-        st.d.nin = nin;
-        st.d.nout = sg.rows;
-        st.d.nstore = nst;
-        st.d.chunks = sg.chunks;
-        st.d.piece_len = sg.nstripes * ess;
-        st.d.spad = sg.nstripes * ess * k;
-        st.d.tile0 = L.tile0[q];
-        st.coef = h_coef + eoff[q];
-        st.entries = (int64_t)(eoff[q + 1] - eoff[q]);
-        st.map = d_map + L.map_off[q] + L.tile0[q];
-        st.ntiles = sg.tiles;
-        // the rows (missing data positions, then the syndrome rows) in the leaf table's order
-        M.resize((size_t)std::max(sg.rows, 1) * nin);
-        solve_rows(sg.num.data(), k, nin, sg.missing.data(), nst, M.data());
-        pack_rows(M.data(), sg.rows, nin, w, h_coef + eoff[q]);
-    }
-    hipError_t e = launch_sized_prep(stage, d_descs, (int)n, c->jt_base, s);
-    if (e != hipSuccess) {  // nothing was queued
-        block_release(c->sized, b, false, s);
-        return hip_fail(e);
-    }
-    for (const sized::Launch &ln : L.launches) {
-        SizedArgs a{};
-        a.desc = d_descs;
-        a.map = d_map + ln.map_off;
-        a.tile_base = ln.tile_base;
-        a.total_tiles = ln.tiles;
-        a.ess = ess;
-        a.cps = ess / 16;
-        a.k = k;
-        a.chk_flag = c->d_chk;
-        e = launch_matmul_sized(a, ln.nw, s);
-        if (e != hipSuccess) break;
-    }
-    if (e == hipSuccess && bad) {
-        // (the block stays this caller's until the counts are read: Decode returns when done)
-        e = hipMemcpyAsync(h_cnt, d_cnt, n * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        bad->assign(n, 0);
-        for (size_t q = 0; q < n && e == hipSuccess; q++) (*bad)[L.idx[q]] = h_cnt[q];
-    }
-    block_release(c->sized, b, true, s);
-    if (e != hipSuccess) return hip_fail(e);
-    c->last_body = EC_BODY_JUMP_TABLE;
-    return after_launch(c->d_chk, s);
+    using Pass = StagedPass<SizedStage>;
+    return staged_pass<SizedStage>(
+        c, c->sized, n, [&](size_t q) -> const SizedSeg & { return *segs[L.idx[q]]; }, &SizedSeg::missing, &L,
+        bad ? n * 4 : 0,  // Decode: the segments' syndrome counters, and where they are read back to
+        [&](SizedStage &st, const SizedSeg &sg, size_t q, const Pass &p) {
+            for (int j = 0; j < st.d.nin; j++) st.d.copy_off[j] = j < k && sg.num[j] < k ? sg.num[j] * ess : -1;
+            for (size_t r = 0; r < sg.missing.size(); r++) st.d.out_off[r] = sg.missing[r] * ess;
+            st.d.out = sg.out;
+            st.d.zero_check = bad ? (uint32_t *)p.d_extra + q : nullptr;
+            st.d.spad = st.d.piece_len * k;
+        },
+        launch_sized_prep,
+        [&](const Pass &p) {
+            hipError_t e = hipSuccess;
+            for (size_t i = 0; i < L.launches.size() && e == hipSuccess; i++) {
+                const sized::Launch &ln = L.launches[i];
+                SizedArgs a{};
+                a.desc = p.desc;
+                a.map = p.map + ln.map_off;
+                a.tile_base = ln.tile_base;
+                a.total_tiles = ln.tiles;
+                a.ess = ess;
+                a.cps = ess / 16;
+                a.k = k;
+                a.chk_flag = c->d_chk;
+                e = launch_matmul_sized(a, ln.nw, s);
+            }
+            return e;
+        },
+        s,
+        [&](const Pass &p) {
+            if (!bad) return hipSuccess;
+            // (the block stays this caller's until the counts are read: Decode returns when done)
+            const uint32_t *h_cnt = (const uint32_t *)p.h_extra;
+            hipError_t e = hipMemcpyAsync(p.h_extra, p.d_extra, n * 4, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            bad->assign(n, 0);
+            for (size_t q = 0; q < n && e == hipSuccess; q++) (*bad)[L.idx[q]] = h_cnt[q];
+            return e;
+        });
 }
 
 int sized_call(ec_ctx *c, size_t nseg, const int *nshares, const int *nums, const uint8_t *const *pieces,
