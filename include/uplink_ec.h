@@ -51,6 +51,8 @@
  *   ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized
  *                            the same with a block count, key and nonce per segment: the
  *                            cipher of a batch of different sizes in one pass
+ *   ec_gcm_open_ranges_sized the open of a byte range of each segment of a batch: ranged
+ *                            downloads (store.go:347-382 Range, eestream/decode.go:199-227)
  *   ec_strerror/ec_format_error  error texts of infectious / eestream
  *
  * Error codes map to the errors eestream's callers test:
@@ -604,6 +606,49 @@ int ec_gcm_open_segments_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *co
  * reference counterpart. */
 int ec_gcm_sized_stats(const ec_ctx *ctx, unsigned long long *seal_launches, unsigned long long *open_launches,
                        unsigned long long *passes);
+/* ---- byte ranges of many segments opened at once (ranged downloads) ----
+ * uplink's Download takes an offset and a length, and the range narrows at every
+ * layer: decryptRanger's Range (streams/store.go:347-382, encryption.Transform)
+ * asks for the cipher blocks CalcEncompassingBlocks(offset, length, in_block)
+ * gives, opens block b under nonce + b for the segment's absolute block
+ * numbers, discards the head of the first block and limits the length;
+ * decodedRanger.Range (eestream/decode.go:199-227) does the same one level down
+ * with the stripes that cover those blocks.  This call is the cipher's part for
+ * a batch of such ranges in one stream-ordered pass.  Segment g is the
+ * nblocks[g] covered blocks first_block[g] .. first_block[g] + nblocks[g] - 1 of
+ * its download's segment: cipher[g] holds exactly those blocks, dense,
+ * nblocks[g] * (in_block + 16) bytes, and out[g] receives the length[g]
+ * plaintext bytes that start head[g] bytes into the first of them -- exactly
+ * length[g] bytes, nothing before or after.  cipher[g] and out[g] may have any
+ * alignment: the path where both and head[g] are multiples of 16 is the sized
+ * open's 16-byte loads and stores, everything else reads and writes narrower.
+ * Relative block r is opened under nonce dev_nonces[12*g..] + (first_block[g] + r)
+ * with prepared key g of dev_keys, so a caller uses the same key and nonce
+ * arrays for a whole open and for any range of it.  Every covered block is
+ * authenticated in full, the parts the range does not want included:
+ * dev_status[g] ends as -1, or as the smallest absolute block number among the
+ * covered blocks whose tag did not verify (the plaintext must then not be used).
+ * nblocks[g] == 0 requires length[g] == 0: the segment is skipped, its pointers
+ * may be NULL and its status is -1.  Staging, passes of at most 4096 segments,
+ * workgroups in proportion to blocks and "everything validated before anything
+ * is queued" are as in ec_gcm_open_segments_sized.  EC_ERR_INVALID_ARG: NULL ctx,
+ * a NULL array with nseg > 0, NULL dev_keys, dev_nonces or dev_status, a NULL
+ * pointer of a segment that is not skipped, head[g] >= in_block, an nblocks[g]
+ * that is not the count CalcEncompassingBlocks(head[g], length[g], in_block)
+ * gives.  EC_ERR_UNSUPPORTED: in_block 0, above 1<<24 or no multiple of 16,
+ * first_block[g] + nblocks[g] above 0x7FFFFFFF (status words are int32), nseg
+ * above 0xFFFFFFFF, a capturing stream.  nseg == 0: EC_OK, nothing queued.
+ * Async on stream.  (The whole-segment encryption.Decrypt branch of
+ * decryptRanger, store.go:360-375, is for inline segments, which never reach
+ * the erasure path: not here.) */
+int ec_gcm_open_ranges_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *const *cipher,
+                             const size_t *first_block, const size_t *nblocks, const size_t *head,
+                             const size_t *length, size_t in_block, const void *dev_keys,
+                             const uint8_t *dev_nonces, uint8_t *const *out, int32_t *dev_status, ec_stream stream);
+/* Cipher launches of the call above on this ctx so far, and its passes (a
+ * diagnostic; ec_gcm_sized_stats does not count them).  Either pointer may be
+ * NULL.  No reference counterpart. */
+int ec_gcm_ranged_stats(const ec_ctx *ctx, unsigned long long *open_launches, unsigned long long *passes);
 /* PadReader padding (single.go:236) on the device: after
  * data_len bytes of each of nseg segments (seg_stride apart) write
  * p = 4 + (block - (data_len+4) % block) % block bytes of byte(p), the last

@@ -29,12 +29,16 @@
 // built on the host by gcm_prepare).  36.6 KB of LDS and 128 VGPRs per
 // workgroup of 4 waves: four workgroups per CU.
 //
-// Two kernels.  gcm_blocks: segments of one block count, a fixed number of
+// Three kernels.  gcm_blocks: segments of one block count, a fixed number of
 // workgroups each (gcm_launch).  gcm_blocks_sized: segments that each have
 // their own block count (ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized);
 // a workgroup finds its segment's descriptor through a per-pass map, and the
 // segment's workgroups run the same stride loop over its blocks
-// (gcm_launch_sized, gcm_sized_geom.hpp).
+// (gcm_launch_sized, gcm_sized_geom.hpp).  gcm_open_ranged: the
+// sized open over a run of covered blocks per segment, block r under nonce +
+// (first block + r), every block authenticated whole and only the wanted bytes
+// [head, head + length) stored, at any alignment (ec_gcm_open_ranges_sized,
+// range_geom.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -257,10 +261,28 @@ __device__ __forceinline__ void gcm_load_nonce(const uint8_t *nonce, uint32_t (&
 // them in its loop; every global access goes through chk.  gcm_blocks keeps its own
 // text: calling this body from it changed its register allocation (scratch 8 / 12
 // bytes per lane became 24 / 28), so only gcm_blocks_sized calls it.
-template <bool kOpen, class Chk>
+//
+// Io is how a 16-byte slot of the block is read and written: GcmDenseIo for
+// gcm_blocks_sized (aligned slots, every one stored), GcmRangedIo for
+// gcm_open_ranged (any alignment, the stores cut to the wanted range).
+struct GcmDenseIo {
+    template <class Chk>
+    __device__ __forceinline__ uint4 load(const Chk &chk, const uint8_t *p) const {
+        return chk.in(p, 16) ? *reinterpret_cast<const uint4 *>(p) : make_uint4(0, 0, 0, 0);  // (skipped: zeros)
+    }
+    // o4: the slot's bytes as big-endian words
+    template <class Chk>
+    __device__ __forceinline__ void store(const Chk &chk, uint8_t *dst, uint32_t sidx, const uint32_t (&o4)[4]) const {
+        if (chk.out(dst + 16ull * sidx, 16))
+            *reinterpret_cast<uint4 *>(dst + 16ull * sidx) =
+                make_uint4(bswap(o4[0]), bswap(o4[1]), bswap(o4[2]), bswap(o4[3]));
+    }
+};
+
+template <bool kOpen, class Chk, class Io = GcmDenseIo>
 __device__ __forceinline__ void gcm_block(const Lds &L, const uint32_t *__restrict__ rk, const uint32_t (&nw)[3],
                                           uint32_t b, const uint8_t *src, uint8_t *dst, const GcmShape &g, int lane,
-                                          int32_t *status, const Chk &chk) {
+                                          int32_t *status, const Chk &chk, const Io &io = Io()) {
     const uint32_t ib = g.ib, slots = g.slots, steps = g.steps, pad = g.pad;
     // nonce + b, little-endian with carry across the 12 bytes; then big-endian words for AES
     uint32_t n0 = nw[0], n1 = nw[1], n2 = nw[2];
@@ -285,14 +307,11 @@ __device__ __forceinline__ void gcm_block(const Lds &L, const uint32_t *__restri
         uint32_t y[4] = {0, 0, 0, 0};
         if (is_data) {
             uint32_t in4[4], o4[4];
-            const uint4 w = chk.in(src + 16ull * sidx, 16) ? *reinterpret_cast<const uint4 *>(src + 16ull * sidx)
-                                                            : make_uint4(0, 0, 0, 0);  // (skipped: zeros)
+            const uint4 w = io.load(chk, src + 16ull * sidx);
             in4[0] = bswap(w.x), in4[1] = bswap(w.y), in4[2] = bswap(w.z), in4[3] = bswap(w.w);
 #pragma unroll
             for (int q = 0; q < 4; q++) o4[q] = in4[q] ^ ks4[q];
-            if (chk.out(dst + 16ull * sidx, 16))
-                *reinterpret_cast<uint4 *>(dst + 16ull * sidx) =
-                    make_uint4(bswap(o4[0]), bswap(o4[1]), bswap(o4[2]), bswap(o4[3]));
+            io.store(chk, dst, sidx, o4);
 #pragma unroll
             for (int q = 0; q < 4; q++) y[q] = kOpen ? in4[q] : o4[q];
         } else if (is_len) {  // len(A) = 0 || len(C) in bits
@@ -592,6 +611,125 @@ __global__ __launch_bounds__(256) void gcm_sized_prep(const GcmSizedStage *stage
     (void)in_block, (void)chk_flag;
 }
 
+// ---- ranges of segments opened in one launch (aesgcm.hpp GcmRangedArgs) ----
+
+// Slot I/O of one covered block of a ranged open.  The block's plaintext byte j
+// belongs at out[rel + j] (rel = the block's first byte minus head, negative only
+// in the first block) and is stored only when that index is inside [0, len).
+// kAligned: every source slot and every output slot address of the segment is
+// 16-byte aligned (aligned pointers, head a multiple of 16): the uint4 load and
+// store of the dense kernel, byte stores only in the slot the range ends in.
+// Otherwise no uint4 or uint32_t is dereferenced at an address that is not so
+// aligned: a misaligned source slot is read byte by byte, a whole slot whose
+// output is 4-byte aligned is stored as four words and everything else as bytes.
+template <bool kAligned>
+struct GcmRangedIo {
+    uint8_t *out;
+    int64_t rel;
+    uint64_t len;
+    bool src16;  // the segment's source slots are 16-byte aligned
+
+    template <class Chk>
+    __device__ __forceinline__ uint4 load(const Chk &chk, const uint8_t *p) const {
+        if (kAligned || src16) return GcmDenseIo().load(chk, p);
+        uint32_t w[4] = {0, 0, 0, 0};
+        if (chk.in(p, 16)) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+        }
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
+
+    template <class Chk>
+    __device__ __forceinline__ void store(const Chk &chk, uint8_t *, uint32_t sidx, const uint32_t (&o4)[4]) const {
+        const int64_t at = rel + 16ll * sidx;        // the slot's byte 0 in out
+        const int64_t left = (int64_t)len - at;      // bytes from there to the end of the range
+        if (at >= 0 && left >= 16) {                 // a whole slot
+            uint8_t *q = out + at;
+            if (kAligned || (reinterpret_cast<uintptr_t>(q) & 15) == 0) {
+                if (chk.out(q, 16))
+                    *reinterpret_cast<uint4 *>(q) = make_uint4(bswap(o4[0]), bswap(o4[1]), bswap(o4[2]), bswap(o4[3]));
+                return;
+            }
+            if ((reinterpret_cast<uintptr_t>(q) & 3) == 0) {
+                if (chk.out(q, 16)) {
+                    uint32_t *w = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) w[i] = bswap(o4[i]);
+                }
+                return;
+            }
+        }
+        if (at <= -16 || left <= 0) return;  // nothing of this slot is wanted
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            if (at + i >= 0 && i < left && chk.out(out + (at + i), 1))
+                out[at + i] = (uint8_t)(o4[i >> 2] >> (24 - 8 * (i & 3)));
+    }
+};
+
+// The stride loop of gcm_blocks_sized over a segment's covered blocks: relative
+// block r is absolute block fb + r for the nonce and the status word.
+template <bool kAligned>
+__device__ __forceinline__ void gcm_ranged_blocks(const Lds &L, const uint32_t *__restrict__ rk, const uint32_t (&nw)[3],
+                                                  const GcmRangedDesc *d, uint32_t wg, const GcmShape &g,
+                                                  int32_t *status, const GcmSizedCheck &chk) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint8_t *in = d->in;
+    uint8_t *out = d->out;
+    const uint32_t nblocks = d->nblocks, fb = d->first_block, wgs = d->wgs;
+    const int64_t head = d->head;
+    const uint64_t len = d->length, in_blk = (uint64_t)g.ib + 16;
+    const bool src16 = (reinterpret_cast<uintptr_t>(in) & 15) == 0;  // (the block stride is a multiple of 16)
+    for (uint32_t r = wg * 4 + wave; r < nblocks; r += wgs * 4) {
+        const GcmRangedIo<kAligned> io{out, (int64_t)((uint64_t)r * g.ib) - head, len, src16};
+        gcm_block<true>(L, rk, nw, fb + r, in + in_blk * r, out, g, lane, status, chk, io);
+    }
+}
+
+// gcm_blocks_sized<true> with a first block, a head and a length per segment: the
+// workgroup -> segment map, the LDS fill and the block body are the same; the
+// segment's flag picks the slot I/O (uniform per workgroup).  kMixed false: a pass
+// in which no segment has the flag, compiled without the bytewise path.
+template <bool kMixed>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UPLINK_GCM_WAVES_PER_EU))) void gcm_open_ranged(
+    GcmRangedArgs a) {
+    __shared__ Lds L;
+    const GcmRangedDesc *d = a.desc + a.map[blockIdx.x];
+    const uint32_t seg = d->seg;
+    const uint32_t wg = blockIdx.x - d->wg0;
+    const GcmSched *ks = a.sched + seg;
+    gcm_fill_lds(L, ks);
+    uint32_t rk[60];
+#pragma unroll
+    for (int i = 0; i < 60; i++) rk[i] = ks->rk[i];  // uniform: scalar loads
+
+    const GcmShape g(a.in_block);
+    uint32_t nw[3];
+    gcm_load_nonce(a.nonces + 12ull * seg, nw);
+    GcmSizedCheck chk;
+#ifdef UPLINK_EC_CHECKED
+    chk = {d->in, d->out, ((uint64_t)g.ib + 16) * d->nblocks, d->length, a.status, a.nseg, a.chk_flag};
+#endif
+    if (kMixed && (d->flags & kGcmRangedBytewise))
+        gcm_ranged_blocks<false>(L, rk, nw, d, wg, g, a.status + seg, chk);
+    else
+        gcm_ranged_blocks<true>(L, rk, nw, d, wg, g, a.status + seg, chk);
+}
+
+// One workgroup per segment of the pass: its descriptor from the host's staging to
+// device memory and its workgroups' entries of the map (as gcm_sized_prep).
+__global__ __launch_bounds__(256) void gcm_ranged_prep(const GcmRangedDesc *stage, GcmRangedDesc *desc, uint32_t *map) {
+    const GcmRangedDesc *st = stage + blockIdx.x;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t *src = reinterpret_cast<const uint64_t *>(st);
+    uint64_t *dst = reinterpret_cast<uint64_t *>(desc + blockIdx.x);
+    for (uint32_t i = tid; i < sizeof(GcmRangedDesc) / 8; i += blockDim.x) dst[i] = src[i];
+    uint32_t *m = map + st->wg0;
+    const uint32_t wgs = st->wgs;
+    for (uint32_t i = tid; i < wgs; i += blockDim.x) m[i] = blockIdx.x;
+}
+
 // ---- host helpers ----
 
 uint32_t sub_word(uint32_t w) {
@@ -731,6 +869,20 @@ hipError_t gcm_launch_sized(const GcmSizedPass &p, bool open, hipStream_t stream
         gcm_blocks_sized<true><<<dim3(p.wgs), 256, 0, stream>>>(a);
     else
         gcm_blocks_sized<false><<<dim3(p.wgs), 256, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t gcm_launch_ranged(const GcmRangedPass &p, hipStream_t stream) {
+    if (p.n == 0 || p.wgs == 0) return hipSuccess;
+    if (p.in_block == 0 || p.in_block > (1u << 24) || p.in_block % 16) return hipErrorInvalidValue;
+    gcm_ranged_prep<<<dim3(p.n), 256, 0, stream>>>(p.stage, p.desc, p.map);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const GcmRangedArgs a{p.desc, p.map, p.sched, p.nonces, p.status, p.chk_flag, p.in_block, p.nseg};
+    if (p.mixed)
+        gcm_open_ranged<true><<<dim3(p.wgs), 256, 0, stream>>>(a);
+    else
+        gcm_open_ranged<false><<<dim3(p.wgs), 256, 0, stream>>>(a);
     return hipGetLastError();
 }
 

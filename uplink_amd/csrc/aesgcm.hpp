@@ -102,6 +102,58 @@ struct GcmSizedPass {
 };
 hipError_t gcm_launch_sized(const GcmSizedPass &p, bool open, hipStream_t stream);
 
+// ---- ranges of segments opened in one launch (include/uplink_ec.h
+// ec_gcm_open_ranges_sized; range_geom.hpp) ----
+//
+// A segment of a pass is a run of nblocks covered blocks, first_block .. of the
+// download's segment, of which the plaintext bytes [head, head + length) are
+// wanted: relative block r is opened under nonce + (first_block + r), every
+// covered block is read and authenticated whole, and only the wanted bytes are
+// stored, dense, at out.  The pass, its map and its workgroups are the sized
+// cipher's (gcm_sized_geom.hpp).
+
+constexpr uint32_t kGcmRangedBytewise = 1;  // GcmRangedDesc::flags: a source or output slot is not 16-byte aligned
+
+// One segment of a pass: written by the host to pinned memory, copied to device
+// memory by gcm_ranged_prep.
+struct GcmRangedDesc {
+    const uint8_t *in;   // nblocks dense blocks of in_block + 16 bytes, at any alignment
+    uint8_t *out;        // length bytes, at any alignment
+    uint64_t length;     // plaintext bytes wanted
+    uint32_t head;       // the first of them is byte `head` of the first covered block (head < in_block)
+    uint32_t nblocks, first_block;
+    uint32_t wg0, wgs;   // its first workgroup in the pass's grid and how many it has
+    uint32_t seg;        // its index in the call: key, nonce and status word
+    uint32_t flags, rsv;
+};
+static_assert(sizeof(GcmRangedDesc) == 56, "copied as 8-byte words");
+
+// Kernel arguments of gcm_open_ranged.
+struct GcmRangedArgs {
+    const GcmRangedDesc *desc;  // the pass's descriptors
+    const uint32_t *map;        // [workgroup] -> position of its segment's descriptor
+    const GcmSched *sched;      // [nseg] of the call
+    const uint8_t *nonces;      // [nseg][12] of the call: each segment's starting nonce
+    int32_t *status;            // [nseg] of the call
+    uint32_t *chk_flag;         // checked build: first access outside a segment's extents (sites 41-43)
+    uint32_t in_block, nseg;
+};
+
+// One pass: the prep launch, then the cipher, on `stream`.
+struct GcmRangedPass {
+    const GcmRangedDesc *stage;  // [n] pinned, device-visible
+    GcmRangedDesc *desc;         // [n] device
+    uint32_t *map;               // [wgs] device
+    uint32_t n, wgs;
+    const GcmSched *sched;
+    const uint8_t *nonces;
+    int32_t *status;
+    uint32_t nseg, in_block;
+    uint32_t *chk_flag;
+    bool mixed;                  // a segment of the pass has kGcmRangedBytewise set
+};
+hipError_t gcm_launch_ranged(const GcmRangedPass &p, hipStream_t stream);
+
 // AES-256 of one block on the host (key setup and tests)
 void aes256_encrypt_block(const uint32_t rk[60], const uint8_t in[16], uint8_t out[16]);
 

@@ -482,6 +482,9 @@ struct ec_ctx {
     StagePool gcm_sized{256u << 10};  // staging of ec_gcm_seal_segments_sized / ec_gcm_open_segments_sized (ec_gcm_sized.cpp)
     // cipher launches of those two calls so far, and their passes (ec_gcm_sized_stats)
     std::atomic<uint64_t> gs_seal{0}, gs_open{0}, gs_passes{0};
+    // cipher launches and passes of ec_gcm_open_ranges_sized so far (ec_gcm_ranged_stats; ec_gcm_ranged.cpp,
+    // staging from gcm_sized too)
+    std::atomic<uint64_t> gr_open{0}, gr_passes{0};
     SlBuilder slb;
 };
 

@@ -12,15 +12,26 @@ are objects.  Here they are one stream-ordered pass on the GPU.
   decode_downloads   the plaintext-sized outputs of a batch of downloads
   open_downloads     the decrypted plaintexts of a batch of decoded downloads
                      (ec_gcm_open_segments_sized)
+
+Ranged downloads.  uplink's Download takes an offset and a length, and the
+range narrows at every layer (store.go:174-253, 347-382; eestream/
+decode.go:199-227), so a 1 MiB read costs about 1 MiB of pieces:
+
+  object_ranges      the (segment, offset, length) triples an object range falls on
+  range_geometry     the blocks, stripes and piece bytes a segment range covers
+  decode_ranges      the covered cipher blocks of a batch of ranges, from piece ranges
+  open_ranges        their plaintext ranges (ec_gcm_open_ranges_sized)
+  download_ranges    the two in stream order
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Sequence, Tuple
 
 from . import _native as N
 from .ecclient import calc_padded
 from .eestream import SegmentCodec, _raise
-from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, DecryptionFailed, open_segments_sized
+from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, DecryptionFailed, open_ranges_sized, open_segments_sized
+from .streams import calc_encompassing_blocks
 
 
 def segment_geometry(size: int, es) -> Tuple[int, int, int]:
@@ -134,6 +145,183 @@ def open_downloads(scheme, sealed: Sequence[Tuple[int, object]], dev_keys, dev_n
                 if block >= 0:
                     raise DecryptionFailed(block)
     return [o[:g[0]] for o, g in zip(outs, geo)], status
+
+
+class RangeGeometry(NamedTuple):
+    """What a plaintext range of one download costs at every layer
+    (range_geometry; uplink_amd/csrc/range_geom.hpp)."""
+    plain_size: int
+    offset: int
+    length: int
+    first_block: int    # fb: the covered cipher blocks are the segment's blocks fb .. fb+nblocks-1
+    nblocks: int
+    head: int           # the range starts head bytes into block fb
+    enc_offset: int     # fb * block_size
+    enc_length: int     # nblocks * block_size
+    first_stripe: int   # fs: the covering stripes are fs .. fs+nstripes-1
+    nstripes: int
+    skip: int           # the covered blocks start skip bytes into the decoded stripes
+    piece_offset: int   # every piece contributes bytes [piece_offset, piece_offset + piece_length)
+    piece_length: int
+
+
+def range_geometry(plain_size: int, offset: int, length: int, es, block_size: int = DEFAULT_BLOCK_SIZE) -> RangeGeometry:
+    """The range [offset, offset+length) of a download of plain_size plaintext
+    bytes, as the reference narrows it: decryptRanger's Range (streams/
+    store.go:347-382, encryption.Transform) asks for the cipher blocks
+    CalcEncompassingBlocks(offset, length, block_size - 16) gives, and
+    decodedRanger.Range (eestream/decode.go:199-227) for the stripes that cover
+    those blocks' encrypted bytes.  A length of 0 covers no block and no stripe.
+    ValueError: a negative value, a range outside [0, plain_size], a block size
+    the cipher does not take, more blocks than a status word counts (first
+    block + blocks above 0x7FFFFFFF).
+
+    Not here: decryptRanger's whole-segment encryption.Decrypt branch
+    (store.go:360-375, an encrypted size that is no multiple of the block).
+    Those are inline segments; they never reach the erasure path."""
+    plain_size, offset, length, block_size = int(plain_size), int(offset), int(length), int(block_size)
+    if plain_size < 0 or offset < 0 or length < 0:
+        raise ValueError("a size, an offset or a length is negative")
+    if offset + length > plain_size:
+        raise ValueError(f"the range ({offset}, {length}) is outside a download of {plain_size} bytes")
+    ib = block_size - TAG_SIZE
+    if ib <= 0 or ib % 16 or ib > 1 << 24:
+        raise ValueError("block_size - 16 is a positive multiple of 16, at most 1<<24")
+    k, ess = es.required_count(), es.erasure_share_size()
+    stripe = k * ess
+    if k <= 0 or ess <= 0:
+        raise ValueError("the erasure scheme has no stripe")
+    fb, nb = calc_encompassing_blocks(offset, length, ib)
+    if fb + nb > 0x7FFFFFFF:
+        raise ValueError("first block + blocks is above 0x7FFFFFFF")
+    if max(plain_size, (fb + nb) * block_size + stripe) >= 1 << 64:
+        raise ValueError("a size does not fit 64 bits")
+    enc_off, enc_len = fb * block_size, nb * block_size
+    fs, ns = calc_encompassing_blocks(enc_off, enc_len, stripe)
+    return RangeGeometry(plain_size, offset, length, fb, nb, offset - fb * ib, enc_off, enc_len, fs, ns,
+                         enc_off - fs * stripe, fs * ess, ns * ess)
+
+
+def object_ranges(segment_plain_sizes: Sequence[int], offset: int, length: int) -> List[Tuple[int, int, int]]:
+    """The (segment index, offset within it, length) triples the range
+    [offset, offset+length) of an object falls on, its segments being
+    segment_plain_sizes in order: Store.Get concatenates one ranger per segment
+    (streams/store.go:174-253).  Segments the range does not touch are absent, a
+    zero-length range gives an empty list, a range beyond the object raises
+    ValueError."""
+    offset, length = int(offset), int(length)
+    sizes = [int(s) for s in segment_plain_sizes]
+    if offset < 0 or length < 0 or any(s < 0 for s in sizes):
+        raise ValueError("a size, an offset or a length is negative")
+    if offset + length > sum(sizes):
+        raise ValueError(f"the range ({offset}, {length}) is outside an object of {sum(sizes)} bytes")
+    res, start, end = [], 0, offset + length
+    for i, s in enumerate(sizes):
+        lo, hi = max(offset, start), min(end, start + s)
+        if lo < hi:
+            res.append((i, lo - start, hi - lo))
+        start += s
+    return res
+
+
+def decode_ranges(scheme, ranges: Sequence[Tuple[RangeGeometry, Dict[int, object]]], *, error_detection: bool = False,
+                  collect_errors: bool = False, stream=None):
+    """decodedRanger.Range (eestream/decode.go:199-227) over a batch: ranges is
+    per download (geometry, {piece number: uint8 device tensor}), the piece
+    *ranges* as fetched -- bytes [piece_offset, piece_offset + piece_length) of
+    each piece that arrived, not whole pieces.  One rebuild_segments_sized (or,
+    with error_detection, decode_segments_sized) call over the nstripes stripes
+    of each.  Returns per download the enc_length-byte view at `skip` into its
+    decoded stripes: the covered cipher blocks, as open_ranges takes them.  A
+    piece of another length raises as EC_ERR_SHARE_SIZE does; error_detection
+    and collect_errors are decode_downloads'."""
+    import torch
+
+    codec = SegmentCodec(scheme)
+    ctx = scheme.ctx
+    stripe = scheme.stripe_size()
+    sets, nstripes, geos = [], [], []
+    dev = None
+    for geo, pieces in ranges:
+        nums = list(pieces.keys())
+        for x in nums:
+            if pieces[x].numel() != geo.piece_length:
+                _raise(ctx, N.EC_ERR_SHARE_SIZE)
+            if dev is None:
+                dev = pieces[x].device
+        sets.append((nums, [pieces[x] for x in nums]))
+        nstripes.append(geo.nstripes)
+        geos.append(geo)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        outs = [torch.empty(g.nstripes * stripe, dtype=torch.uint8, device=dev) for g in geos]
+        ptrs = [o if o.numel() else None for o in outs]
+        errors: List[object] = [None] * len(outs)
+        if error_detection:
+            codes = codec.decode_segments_sized(sets, nstripes, ptrs, stream=stream, collect=collect_errors)
+            errors = [_error_of(ctx, c) for c in codes]
+        else:
+            codec.rebuild_segments_sized(sets, nstripes, ptrs, stream=stream)
+    res = [o[g.skip:g.skip + g.enc_length] for o, g in zip(outs, geos)]
+    return (res, errors) if collect_errors else res
+
+
+def open_ranges(scheme, sealed: Sequence[Tuple[RangeGeometry, object]], dev_keys, dev_nonces, *,
+                block_size: int = DEFAULT_BLOCK_SIZE, check: bool = False, stream=None):
+    """decryptRanger's Range (streams/store.go:347-382) over a batch
+    (ec_gcm_open_ranges_sized): sealed is per download (geometry, enc), `enc`
+    the uint8 device tensor of exactly the enc_length bytes of its covered
+    blocks, at any alignment, as decode_ranges returns it; another length raises
+    ValueError.  Download g is opened under prepared key g of dev_keys and
+    nonce dev_nonces[12*g:12*g+12] + its absolute block numbers: the key and
+    nonce arrays of a whole open.  Returns (plains, status): plains[g] is a
+    device tensor of exactly `length` bytes and status the [nseg] int32 device
+    tensor, -1 or the smallest absolute number of a covered block of download g
+    whose tag did not verify -- every covered block is authenticated whole.
+    check=True behaves as in open_downloads."""
+    import torch
+
+    ib = int(block_size) - TAG_SIZE
+    dev = None
+    for geo, enc in sealed:
+        if enc.dtype != torch.uint8 or not enc.is_contiguous():
+            raise ValueError("a download's covered blocks are a contiguous uint8 tensor")
+        if enc.numel() != geo.enc_length or geo.enc_length != geo.nblocks * int(block_size):
+            raise ValueError(f"a range of {geo.nblocks} blocks has {geo.nblocks * int(block_size)} encrypted bytes, "
+                             f"got {enc.numel()}")
+        if dev is None:
+            dev = enc.device
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    geos = [g for g, _ in sealed]
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        outs = [torch.empty(g.length, dtype=torch.uint8, device=dev) for g in geos]
+        status = torch.empty(len(geos), dtype=torch.int32, device=dev)
+        if geos:
+            open_ranges_sized(scheme, [e if g.nblocks else None for g, e in sealed], [g.first_block for g in geos],
+                              [g.nblocks for g in geos], [g.head for g in geos], [g.length for g in geos], ib, dev_keys,
+                              dev_nonces, [o if o.numel() else None for o in outs], status, stream=stream)
+        if check:
+            if stream is not None and ts is None:  # a raw stream handle: not the stream the copy below runs on
+                torch.cuda.synchronize()
+            for block in status.cpu().tolist():  # (a copy on the current stream: it waits for the open)
+                if block >= 0:
+                    raise DecryptionFailed(block)
+    return outs, status
+
+
+def download_ranges(scheme, ranges: Sequence[Tuple[RangeGeometry, Dict[int, object]]], dev_keys, dev_nonces, *,
+                    block_size: int = DEFAULT_BLOCK_SIZE, error_detection: bool = False, check: bool = False,
+                    stream=None):
+    """decode_ranges then open_ranges in stream order: the piece ranges of a
+    batch of downloads in, (plains, status) out -- plains[g] the bytes
+    [offset, offset+length) of download g's plaintext."""
+    encs = decode_ranges(scheme, ranges, error_detection=error_detection, stream=stream)
+    return open_ranges(scheme, [(g, e) for (g, _), e in zip(ranges, encs)], dev_keys, dev_nonces,
+                       block_size=block_size, check=check, stream=stream)
 
 
 class _Null:

@@ -201,6 +201,27 @@ def open_segments_sized(scheme, ciphers, nblocks, in_block: int, dev_keys, dev_n
     _raise(scheme.ctx, rc)
 
 
+def open_ranges_sized(scheme, ciphers, first_block, nblocks, head, length, in_block: int, dev_keys, dev_nonces, outs,
+                      dev_status, stream=None):
+    """ec_gcm_open_ranges_sized: ciphers[g] is the nblocks[g]*(in_block+16)
+    bytes of the covered blocks first_block[g].. of segment g, outs[g] the
+    length[g] plaintext bytes that start head[g] bytes into the first of them;
+    any alignment.  dev_status[g] ends as -1 or the smallest absolute number of
+    a covered block that failed."""
+    from .eestream import SegmentCodec as C
+    nseg, c_in, c_nb, c_out = _sized_lists("ciphertext", ciphers, nblocks, outs)
+    per = []
+    for name, v in (("first block", first_block), ("head", head), ("length", length)):
+        v = [int(x) for x in v]
+        if len(v) != nseg or any(x < 0 for x in v):
+            raise ValueError(f"one non-negative {name} per segment")
+        per.append((ctypes.c_size_t * max(nseg, 1))(*v))
+    rc = N.load().ec_gcm_open_ranges_sized(scheme.ctx, nseg, c_in, per[0], c_nb, per[1], per[2], int(in_block),
+                                           C._addr(dev_keys), C._addr(dev_nonces), c_out, C._addr(dev_status),
+                                           C._stream(stream))
+    _raise(scheme.ctx, rc)
+
+
 def open_segments(cipher, nseg: int, nblocks: int, in_block: int, dev_keys, dev_nonces, out, dev_status,
                   stream=None):
     """ec_gcm_open_segments; dev_status[g] = -1 or the first failing block."""
