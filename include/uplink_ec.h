@@ -640,7 +640,7 @@ int ec_gcm_sized_stats(const ec_ctx *ctx, unsigned long long *seal_launches, uns
  * above 0xFFFFFFFF, a capturing stream.  nseg == 0: EC_OK, nothing queued.
  * Async on stream.  (The whole-segment encryption.Decrypt branch of
  * decryptRanger, store.go:360-375, is for inline segments, which never reach
- * the erasure path: not here.) */
+ * the erasure path: that one is ec_gcm_open_messages below.) */
 int ec_gcm_open_ranges_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *const *cipher,
                              const size_t *first_block, const size_t *nblocks, const size_t *head,
                              const size_t *length, size_t in_block, const void *dev_keys,
@@ -649,6 +649,58 @@ int ec_gcm_open_ranges_sized(const ec_ctx *ctx, size_t nseg, const uint8_t *cons
  * diagnostic; ec_gcm_sized_stats does not count them).  Either pointer may be
  * NULL.  No reference counterpart. */
 int ec_gcm_ranged_stats(const ec_ctx *ctx, unsigned long long *open_launches, unsigned long long *passes);
+/* ---- one-shot messages, a raw key each (inline segments, content keys, metadata) ----
+ * Beside the block transform the stream layer calls the cipher in a second
+ * form, aesgcm.Seal(nil, nonce[:12], data, nil) over one whole message with no
+ * block framing and no padding:
+ *   encryption.Encrypt(inline, cipher, &contentKey, &nonce) for an object of up
+ *     to maxInlineSize = 4096 bytes, which is never erasure coded
+ *     (splitter/splitter.go:189, project.go:24), and encryption.Decrypt of it,
+ *     the whole-segment branch of decryptRanger (streams/store.go:360-375);
+ *   encryption.EncryptKey / DecryptKey, a 32-byte key sealed to 48 bytes: every
+ *     segment's content key (splitter.go:160, store.go:349) and the metadata key
+ *     (uploader.go:415, metaclient/objects.go:169,897,1105, move.go:110-154);
+ *   Encrypt / Decrypt of stream info and ETags (uploader.go:421,438,
+ *     objects.go:1111,1122, multipart_iterators.go:366).
+ * These two calls do that for a list of messages in one stream-ordered pass.
+ * Message i is len[i] plaintext bytes (0 .. 1<<24) under the 32 raw key bytes
+ * dev_keys32[32*i ..] and the nonce dev_nonces[12*i ..], both in device memory at
+ * any alignment: J0 = nonce || 00000001, the counter runs from 2, GHASH over the
+ * zero-padded ciphertext and the length block with no AAD, tag = GHASH ^
+ * AES_K(J0).  len[i] is the plaintext length in both calls; the sealed form is
+ * len[i] + 16 bytes, ciphertext || tag.  Everything is derived from the key bytes
+ * on the GPU: there is no ec_gcm_prepare_keys and no prepared-key buffer here.
+ * plain[i], cipher[i] and out[i] may have any alignment (16-byte loads and
+ * stores where an address allows them, narrower ones otherwise); a message's
+ * input and output must not overlap each other or another message's.
+ * len[i] == 0 is a real message: the seal writes its 16-byte tag, the open
+ * checks it; plain[i] of the seal and out[i] of the open may then be NULL.
+ * The open authenticates a message before it releases anything of it:
+ * dev_status[i] ends as 0, or as 1 when the tag does not verify, and then
+ * exactly len[i] zero bytes are written to out[i] (Go's Open leaves no plaintext
+ * behind).  A failing message does not disturb the others.
+ * One wave of the GPU takes one message, so the calls are for many short
+ * messages; a long one is correct (its wave's 64 lanes share it) but gets no
+ * more than that wave.  ctx supplies only the device and a staging pool:
+ * descriptors are staged in event-recycled blocks in passes of a fixed number of
+ * messages (ec_gcm_messages_stats), and no caller memory is retained after
+ * return.  Everything is validated before anything is queued: on an error
+ * nothing is written.  EC_ERR_INVALID_ARG: NULL ctx, a NULL array with nmsg > 0,
+ * NULL dev_keys32 or dev_nonces, NULL dev_status (open), a NULL pointer of a
+ * message other than the two len[i] == 0 cases above.  EC_ERR_UNSUPPORTED:
+ * len[i] above 1<<24, nmsg above 0xFFFFFFFF, a capturing stream.  nmsg == 0:
+ * EC_OK, nothing queued.  Async on stream, no host synchronisation once the
+ * pool is warm. */
+int ec_gcm_seal_messages(const ec_ctx *ctx, size_t nmsg, const uint8_t *const *plain, const size_t *len,
+                         const uint8_t *dev_keys32, const uint8_t *dev_nonces, uint8_t *const *out, ec_stream stream);
+int ec_gcm_open_messages(const ec_ctx *ctx, size_t nmsg, const uint8_t *const *cipher, const size_t *len,
+                         const uint8_t *dev_keys32, const uint8_t *dev_nonces, uint8_t *const *out,
+                         int32_t *dev_status, ec_stream stream);
+/* Cipher launches of the two calls above on this ctx so far (a diagnostic): of
+ * the seal, of the open, the passes of both, and the messages a pass holds (a
+ * constant of the build).  Any pointer may be NULL.  No reference counterpart. */
+int ec_gcm_messages_stats(const ec_ctx *ctx, unsigned long long *seal_launches, unsigned long long *open_launches,
+                          unsigned long long *passes, unsigned long long *pass_messages);
 /* PadReader padding (single.go:236) on the device: after
  * data_len bytes of each of nseg segments (seg_stride apart) write
  * p = 4 + (block - (data_len+4) % block) % block bytes of byte(p), the last

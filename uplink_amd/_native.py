@@ -137,6 +137,11 @@ SIGNATURES = {
                                  [ctypes.POINTER(ctypes.c_size_t)] * 4 +
                                  [ctypes.c_size_t, vp, vp, ctypes.POINTER(vp), vp, vp]),
     "ec_gcm_ranged_stats": (ctypes.c_int, [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 2),
+    "ec_gcm_seal_messages": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                            vp, vp, ctypes.POINTER(vp), vp]),
+    "ec_gcm_open_messages": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                            vp, vp, ctypes.POINTER(vp), vp, vp]),
+    "ec_gcm_messages_stats": (ctypes.c_int, [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 4),
     "ec_pad_segments": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_size_t, vp]),
     "ec_gcm_seal_host": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]),
     "ec_gcm_open_host": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp,

@@ -39,6 +39,12 @@
 // (first block + r), every block authenticated whole and only the wanted bytes
 // [head, head + length) stored, at any alignment (ec_gcm_open_ranges_sized,
 // range_geom.hpp).
+//
+// A fourth kernel stands beside them: gcm_messages, the cipher's other form in
+// the stream layer -- one whole message of any length per seal, no blocks, a raw
+// 32-byte key per message and no GcmSched (ec_gcm_seal_messages /
+// ec_gcm_open_messages; gcm_msg_device.hpp, gcm_msg_geom.hpp).  It
+// shares the T-table AES below and nothing of the per-key GHASH tables.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -46,6 +52,8 @@
 #include <vector>
 
 #include "aesgcm.hpp"
+#include "gcm_msg_device.hpp"
+#include "gcm_msg_geom.hpp"
 
 namespace uplink_ec {
 namespace {
@@ -137,15 +145,16 @@ struct Lds {
     uint16_t rem8[256];          // (16 bits each: with three workgroups' tables the CU's LDS is full)
 };
 
-// Tk[x] for this lane
-template <int k>
-__device__ __forceinline__ uint32_t T(const Lds &L, uint32_t x, uint32_t copy) {
+// Tk[x] for this lane (LdsT: a workgroup's LDS whose member t is the T-table)
+template <int k, class LdsT>
+__device__ __forceinline__ uint32_t T(const LdsT &L, uint32_t x, uint32_t copy) {
     const uint32_t v = L.t[x * kCopies + copy];
     return k ? __builtin_amdgcn_alignbit(v, v, 8 * k) : v;
 }
 
 // AES-256 of the big-endian words s[4] with round keys rk (SGPRs), T-tables in LDS
-__device__ __forceinline__ void aes_encrypt(uint32_t (&s)[4], const uint32_t *__restrict__ rk, const Lds &L) {
+template <class LdsT>
+__device__ __forceinline__ void aes_encrypt(uint32_t (&s)[4], const uint32_t *__restrict__ rk, const LdsT &L) {
     const uint32_t cp = threadIdx.x % kCopies;
     uint32_t a = s[0] ^ rk[0], b = s[1] ^ rk[1], c = s[2] ^ rk[2], d = s[3] ^ rk[3];
 #pragma unroll
@@ -519,7 +528,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UPLINK_GCM_
 // call's status words.  An access outside is skipped and its site recorded (as
 // blake3.hip in_piece / list_store_ok); in the product build every access passes
 // and the struct is empty.
-struct GcmSizedCheck {
+template <int kSiteIn, int kSiteOut, int kSiteStatus>
+struct GcmCheck {
 #ifdef UPLINK_EC_CHECKED
     const uint8_t *in_lo, *out_lo;
     uint64_t in_len, out_len;
@@ -532,10 +542,10 @@ struct GcmSizedCheck {
         if (flag) atomicCAS(flag, 0u, (uint32_t)site);
         return false;
     }
-    __device__ __forceinline__ bool in(const void *p, uint32_t bytes) const { return span(p, bytes, in_lo, in_len, kSiteGcmIn); }
-    __device__ __forceinline__ bool out(const void *p, uint32_t bytes) const { return span(p, bytes, out_lo, out_len, kSiteGcmOut); }
+    __device__ __forceinline__ bool in(const void *p, uint32_t bytes) const { return span(p, bytes, in_lo, in_len, kSiteIn); }
+    __device__ __forceinline__ bool out(const void *p, uint32_t bytes) const { return span(p, bytes, out_lo, out_len, kSiteOut); }
     __device__ __forceinline__ bool status(const void *p) const {
-        return span(p, 4, reinterpret_cast<const uint8_t *>(st_lo), 4ull * nseg, kSiteGcmStatus);
+        return span(p, 4, reinterpret_cast<const uint8_t *>(st_lo), 4ull * nseg, kSiteStatus);
     }
 #else
     __device__ __forceinline__ bool in(const void *, uint32_t) const { return true; }
@@ -543,6 +553,7 @@ struct GcmSizedCheck {
     __device__ __forceinline__ bool status(const void *) const { return true; }
 #endif
 };
+using GcmSizedCheck = GcmCheck<kSiteGcmIn, kSiteGcmOut, kSiteGcmStatus>;
 
 // A workgroup finds its segment through the pass's map (uniform per workgroup:
 // scalar loads), fills its LDS with that segment's key and runs gcm_blocks' stride
@@ -730,6 +741,252 @@ __global__ __launch_bounds__(256) void gcm_ranged_prep(const GcmRangedDesc *stag
     for (uint32_t i = tid; i < wgs; i += blockDim.x) m[i] = blockIdx.x;
 }
 
+// ---- one-shot messages, a raw key each (aesgcm.hpp GcmMsgArgs) ----
+
+[[maybe_unused]] constexpr int kSiteMsgIn = 51, kSiteMsgOut = 52, kSiteMsgStatus = 53;  // (checked build)
+using GcmMsgCheck = GcmCheck<kSiteMsgIn, kSiteMsgOut, kSiteMsgStatus>;
+
+// The multiply by the wave's current multiplier (gcm_msg_device.hpp): 1, on a
+// 4-bit table of it that 16 lanes of the wave build in LDS; 0, bit by bit with the
+// multiplier's run of shifts in scalar registers.  DESIGN.md 4n has both measured.
+#ifndef UPLINK_GCM_MSG_MUL  // (-D for A/B builds)
+#define UPLINK_GCM_MSG_MUL 1
+#endif
+
+struct MsgLds {
+    uint32_t t[256 * kCopies];
+    alignas(16) uint32_t tab[gcmmsg::kWaves][16][4];  // a wave's table of its current multiplier
+};
+
+__device__ __forceinline__ gcmmsg::Block msg_uniform(const gcmmsg::Block &b) {  // (the same in every lane: to SGPRs)
+    return {{(uint32_t)__builtin_amdgcn_readfirstlane(b.w[0]), (uint32_t)__builtin_amdgcn_readfirstlane(b.w[1]),
+             (uint32_t)__builtin_amdgcn_readfirstlane(b.w[2]), (uint32_t)__builtin_amdgcn_readfirstlane(b.w[3])}};
+}
+
+struct MsgMulBits {
+    gcmmsg::Block m;
+    __device__ __forceinline__ void set(const gcmmsg::Block &x, int) { m = msg_uniform(x); }
+    __device__ __forceinline__ gcmmsg::Block mul(const gcmmsg::Block &x) const { return gcmmsg::gf_mul_bits(x, m); }
+};
+
+// Only the table's own wave touches it, and a wave's LDS accesses are served in
+// order: the fences keep the compiler from moving one lane's reads across the
+// other lanes' writes.
+struct MsgMulTable {
+    uint32_t (*tab)[4];
+    __device__ __forceinline__ void set(const gcmmsg::Block &x, int lane) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 16) {
+            const gcmmsg::Block e = gcmmsg::gf_table_entry(x, (uint32_t)lane);
+            *reinterpret_cast<uint4 *>(tab[lane]) = make_uint4(e.w[0], e.w[1], e.w[2], e.w[3]);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ gcmmsg::Block mul(const gcmmsg::Block &x) const {
+        uint32_t (*t)[4] = tab;
+        return gcmmsg::gf_mul_table(x, [t](uint32_t n) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(t[n]);
+            return gcmmsg::Block{{v.x, v.y, v.z, v.w}};
+        });
+    }
+};
+#if UPLINK_GCM_MSG_MUL
+using MsgMul = MsgMulTable;
+#else
+using MsgMul = MsgMulBits;
+#endif
+
+// How a message's 16-byte slots are read and written.  A slot is read with one
+// 16-byte load when the message's source is 16-byte aligned, and written with one
+// 16-byte store when its destination is, with four words when that is 4-byte
+// aligned; everything else, and the message's short last slot, goes byte by byte.
+// No uint4 or uint32_t is dereferenced at an address that is not so aligned.
+struct GcmMsgIo {
+    bool src16, dst16, dst4;  // (the same for every slot of a message: slots are 16 bytes apart)
+
+    // n bytes at p as a zero-padded block
+    __device__ __forceinline__ gcmmsg::Block load(const GcmMsgCheck &chk, const uint8_t *p, uint32_t n) const {
+        if (n == 16 && src16) {
+            const uint4 w = GcmDenseIo().load(chk, p);
+            return {{bswap(w.x), bswap(w.y), bswap(w.z), bswap(w.w)}};
+        }
+        gcmmsg::Block r = gcmmsg::zero_block();
+        if (chk.in(p, n)) {
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++)  // (unrolled: no word of r is indexed by a run-time value)
+                if (i < n) r.w[i >> 2] |= (uint32_t)p[i] << (24 - 8 * (i & 3));
+        }
+        return r;
+    }
+    // the first n bytes of o to q
+    __device__ __forceinline__ void store(const GcmMsgCheck &chk, uint8_t *q, uint32_t n, const gcmmsg::Block &o) const {
+        if (!chk.out(q, n)) return;
+        if (n == 16 && dst16) {
+            *reinterpret_cast<uint4 *>(q) = make_uint4(bswap(o.w[0]), bswap(o.w[1]), bswap(o.w[2]), bswap(o.w[3]));
+        } else if (n == 16 && dst4) {
+            uint32_t *w = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+            for (int i = 0; i < 4; i++) w[i] = bswap(o.w[i]);
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++)
+                if (i < n) q[i] = gcmmsg::block_byte(o, i);
+        }
+    }
+};
+
+// byte i (0..15) of b without indexing its words by a run-time value
+__device__ __forceinline__ uint8_t msg_byte(const gcmmsg::Block &b, uint32_t i) {
+    const uint32_t w = i < 8 ? (i < 4 ? b.w[0] : b.w[1]) : (i < 12 ? b.w[2] : b.w[3]);
+    return (uint8_t)(w >> (24 - 8 * (i & 3)));
+}
+
+// One wave per message, gcmmsg::kWaves messages per workgroup; the seal and the
+// open are two instantiations of this body.  The wave expands the message's key
+// (the S-box is a byte of the T-table in LDS), takes H = AES_K(0) and AES_K(J0)
+// in one AES (even and odd lanes), then every lane takes `rounds` consecutive
+// slots of the front-padded message (gcm_msg_geom.hpp): AES-CTR on them (seal)
+// and a Horner GHASH with H, while H^rounds is run up beside it; the lanes'
+// partial sums are folded pairwise with H^rounds, its square, ... (gcm_msg_device.hpp).
+// The open authenticates first and only then runs the counter blocks, so nothing
+// of a message whose tag does not verify is released: its output is zeros.
+template <bool kOpen>
+__global__ __launch_bounds__(64 * gcmmsg::kWaves) void gcm_messages(GcmMsgArgs a) {
+    using namespace gcmmsg;
+    __shared__ MsgLds L;
+    for (int i = threadIdx.x; i < 256 * kCopies; i += blockDim.x) L.t[i] = kAesDev.t0[i / kCopies];
+    __syncthreads();  // (the only workgroup barrier: a wave without a message leaves after it)
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t q = blockIdx.x * kWaves + wave;
+    if (q >= a.n) return;
+    const GcmMsgDesc *d = a.desc + q;
+    const uint8_t *src = d->in;
+    uint8_t *dst = d->out;
+    const uint32_t len = d->len, msg = d->msg;
+    GcmMsgCheck chk;
+#ifdef UPLINK_EC_CHECKED
+    chk = {src, dst, (uint64_t)len + (kOpen ? kTagBytes : 0), (uint64_t)len + (kOpen ? 0 : kTagBytes), a.status, a.nmsg,
+           a.chk_flag};
+#endif
+    const GcmMsgIo io{(reinterpret_cast<uintptr_t>(src) & 15) == 0, (reinterpret_cast<uintptr_t>(dst) & 15) == 0,
+                      (reinterpret_cast<uintptr_t>(dst) & 3) == 0};
+
+    // the round keys, from the 32 key bytes (any alignment): the same in every lane, then scalar
+    uint32_t rk[60];
+    {
+        const uint8_t *kp = a.keys + 32ull * msg;
+        uint32_t kw[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) kw[i] = __builtin_amdgcn_readfirstlane(load_be32(kp + 4 * i));
+        const uint32_t cp = threadIdx.x % kCopies;
+        const uint32_t *tt = L.t;
+        key_expand(kw, rk, [tt, cp](uint32_t x) { return (tt[x * kCopies + cp] >> 8) & 0xffu; });  // T0 byte 1 = S[x]
+#pragma unroll
+        for (int i = 0; i < 60; i++) rk[i] = __builtin_amdgcn_readfirstlane(rk[i]);
+    }
+    uint32_t nw[3];
+    {
+        const uint8_t *np = a.nonces + 12ull * msg;
+#pragma unroll
+        for (int i = 0; i < 3; i++) nw[i] = __builtin_amdgcn_readfirstlane(load_be32(np + 4 * i));
+    }
+    // H = AES_K(0) on the even lanes, AES_K(J0), the tag's mask, on the odd ones
+    Block h, ekj0;
+    {
+        uint32_t s4[4] = {0, 0, 0, 0};
+        if (lane & 1) s4[0] = nw[0], s4[1] = nw[1], s4[2] = nw[2], s4[3] = 1;
+        aes_encrypt(s4, rk, L);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            h.w[i] = __builtin_amdgcn_readlane(s4[i], 0);
+            ekj0.w[i] = __builtin_amdgcn_readlane(s4[i], 1);
+        }
+    }
+
+    const uint32_t R = rounds(len), pad = front_pad(len), nd = data_slots(len), tail = tail_bytes(len);
+    MsgMul mul{};
+#if UPLINK_GCM_MSG_MUL
+    mul.tab = L.tab[wave];
+#endif
+    mul.set(h, lane);
+
+    // lane `lane` takes padded slots lane * R .. lane * R + R - 1; the length block is the last of lane 63
+    Block acc = zero_block(), hr = h;
+    for (uint32_t j = 0; j < R; j++) {
+        const uint32_t t = (uint32_t)lane * R + j;
+        const bool is_len = t + 1 == R * kLanes;
+        const bool is_data = t >= pad && !is_len;
+        const uint32_t sidx = t - pad;
+        Block y = zero_block();
+        if (is_data) {
+            const uint32_t n = sidx + 1 == nd ? tail : 16;
+            const Block in = io.load(chk, src + 16ull * sidx, n);
+            if (kOpen) {
+                y = in;
+            } else {
+                uint32_t ks4[4] = {nw[0], nw[1], nw[2], 2 + sidx};
+                aes_encrypt(ks4, rk, L);
+                const Block o = in ^ Block{{ks4[0], ks4[1], ks4[2], ks4[3]}};
+                io.store(chk, dst + 16ull * sidx, n, o);
+                y = keep_bytes(o, n);  // GHASH sees the zero-padded ciphertext
+            }
+        } else if (is_len) {
+            y = length_block(len);
+        }
+        acc = horner_step(acc, y, mul);
+        if (j) hr = mul.mul(hr);  // H^R beside it (the same in every lane)
+    }
+
+    // the pairwise combination; a step whose lower lanes hold only front padding is skipped
+    const uint32_t steps = combine_steps(len);
+    for (uint32_t s = 0; s < steps; s++) {
+        const int dist = 1 << s;
+        mul.set(hr, lane);
+        Block partner;
+#pragma unroll
+        for (int i = 0; i < 4; i++) partner.w[i] = __shfl_xor(acc.w[i], dist);
+        acc = combine_step(acc, partner, (lane & dist) != 0, mul);
+        if (s + 1 < steps) hr = mul.mul(hr);
+    }
+    // lane 63 holds the GHASH (with fewer than six steps the lanes below the folded ones do not)
+    Block tag;
+#pragma unroll
+    for (int i = 0; i < 4; i++) tag.w[i] = __builtin_amdgcn_readlane(acc.w[i], 63) ^ ekj0.w[i];
+
+    if (!kOpen) {
+        if (lane < 16 && chk.out(dst + len + lane, 1)) dst[(uint64_t)len + lane] = msg_byte(tag, lane);
+        return;
+    }
+    bool differs = false;
+    if (lane < 16 && chk.in(src + len + lane, 1)) differs = src[(uint64_t)len + lane] != msg_byte(tag, lane);
+    const bool ok = __ballot(differs) == 0;
+    if (lane == 0 && chk.status(a.status + msg)) a.status[msg] = ok ? 0 : 1;
+    for (uint32_t j = 0; j < R; j++) {
+        const uint32_t t = (uint32_t)lane * R + j;
+        if (t < pad || t + 1 == R * kLanes) continue;
+        const uint32_t sidx = t - pad;
+        const uint32_t n = sidx + 1 == nd ? tail : 16;
+        Block o = zero_block();
+        if (ok) {
+            uint32_t ks4[4] = {nw[0], nw[1], nw[2], 2 + sidx};
+            aes_encrypt(ks4, rk, L);
+            o = io.load(chk, src + 16ull * sidx, n) ^ Block{{ks4[0], ks4[1], ks4[2], ks4[3]}};
+        }
+        io.store(chk, dst + 16ull * sidx, n, o);
+    }
+}
+
+// The pass's descriptors from the host's staging to device memory.
+__global__ __launch_bounds__(256) void gcm_msg_prep(const GcmMsgDesc *stage, GcmMsgDesc *desc, uint32_t n) {
+    const uint64_t *src = reinterpret_cast<const uint64_t *>(stage);
+    uint64_t *dst = reinterpret_cast<uint64_t *>(desc);
+    const uint32_t words = n * (uint32_t)(sizeof(GcmMsgDesc) / 8);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
 // ---- host helpers ----
 
 uint32_t sub_word(uint32_t w) {
@@ -883,6 +1140,22 @@ hipError_t gcm_launch_ranged(const GcmRangedPass &p, hipStream_t stream) {
         gcm_open_ranged<true><<<dim3(p.wgs), 256, 0, stream>>>(a);
     else
         gcm_open_ranged<false><<<dim3(p.wgs), 256, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t gcm_launch_messages(const GcmMsgPass &p, bool open, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    if (p.n > gcmmsg::kPassMessages) return hipErrorInvalidValue;
+    const uint32_t words = p.n * (uint32_t)(sizeof(GcmMsgDesc) / 8);
+    gcm_msg_prep<<<dim3((words + 255) / 256), 256, 0, stream>>>(p.stage, p.desc, p.n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const GcmMsgArgs a{p.desc, p.keys, p.nonces, p.status, p.chk_flag, p.n, p.nmsg};
+    const dim3 grid(gcmmsg::pass_workgroups(p.n)), block(64 * gcmmsg::kWaves);
+    if (open)
+        gcm_messages<true><<<grid, block, 0, stream>>>(a);
+    else
+        gcm_messages<false><<<grid, block, 0, stream>>>(a);
     return hipGetLastError();
 }
 

@@ -154,6 +154,50 @@ struct GcmRangedPass {
 };
 hipError_t gcm_launch_ranged(const GcmRangedPass &p, hipStream_t stream);
 
+// ---- one-shot messages, a raw key each (include/uplink_ec.h
+// ec_gcm_seal_messages / ec_gcm_open_messages; gcm_msg_geom.hpp,
+// gcm_msg_device.hpp) ----
+//
+// A message is one GCM seal or open of len bytes (0 .. 1 << 24) under its own
+// 32-byte key and 12-byte nonce: J0 = nonce || 1, counters from 2, no AAD, the
+// sealed form ciphertext || tag.  One wave takes a message and derives everything
+// from the key bytes itself -- round keys, H, the powers of H its layout needs --
+// so there is no GcmSched and no host-side key preparation.  Meant for many short
+// messages (inline segments up to 4 KiB, 32-byte content keys); a long message is
+// still spread over its wave's 64 lanes, but one wave is all it gets.
+
+// One message of a pass: written by the host to pinned memory, copied to device
+// memory by gcm_msg_prep.
+struct GcmMsgDesc {
+    const uint8_t *in;  // len bytes to seal, len + 16 to open; any alignment
+    uint8_t *out;       // len + 16 bytes sealed, len opened; any alignment
+    uint32_t len;
+    uint32_t msg;       // its index in the call: key, nonce and status word
+};
+static_assert(sizeof(GcmMsgDesc) == 24, "copied as 8-byte words");
+
+// Kernel arguments of gcm_messages.
+struct GcmMsgArgs {
+    const GcmMsgDesc *desc;  // the pass's descriptors
+    const uint8_t *keys;     // [nmsg][32] of the call, raw key bytes
+    const uint8_t *nonces;   // [nmsg][12] of the call
+    int32_t *status;         // [nmsg] of the call (open): 0, or 1 when the tag did not verify
+    uint32_t *chk_flag;      // checked build: first access outside a message's extents (sites 51-53)
+    uint32_t n, nmsg;        // messages of the pass, of the call
+};
+
+// One pass: the prep launch, then the cipher, on `stream`.
+struct GcmMsgPass {
+    const GcmMsgDesc *stage;  // [n] pinned, device-visible
+    GcmMsgDesc *desc;         // [n] device
+    uint32_t n;
+    const uint8_t *keys, *nonces;
+    int32_t *status;
+    uint32_t nmsg;
+    uint32_t *chk_flag;
+};
+hipError_t gcm_launch_messages(const GcmMsgPass &p, bool open, hipStream_t stream);
+
 // AES-256 of one block on the host (key setup and tests)
 void aes256_encrypt_block(const uint32_t rk[60], const uint8_t in[16], uint8_t out[16]);
 

@@ -485,6 +485,9 @@ struct ec_ctx {
     // cipher launches and passes of ec_gcm_open_ranges_sized so far (ec_gcm_ranged_stats; ec_gcm_ranged.cpp,
     // staging from gcm_sized too)
     std::atomic<uint64_t> gr_open{0}, gr_passes{0};
+    // cipher launches of ec_gcm_seal_messages / ec_gcm_open_messages so far and the passes of both
+    // (ec_gcm_messages_stats; ec_gcm_messages.cpp, staging from gcm_sized too)
+    std::atomic<uint64_t> gm_seal{0}, gm_open{0}, gm_passes{0};
     SlBuilder slb;
 };
 

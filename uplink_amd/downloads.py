@@ -22,6 +22,14 @@ decode.go:199-227), so a 1 MiB read costs about 1 MiB of pieces:
   decode_ranges      the covered cipher blocks of a batch of ranges, from piece ranges
   open_ranges        their plaintext ranges (ec_gcm_open_ranges_sized)
   download_ranges    the two in stream order
+
+Inline segments.  An object of up to 4 KiB is never erasure coded: its whole
+ciphertext is one GCM message under its content key, itself sealed under the
+derived key (streams/store.go:349, 360-375):
+
+  open_content_keys      DecryptKey for a batch (ec_gcm_open_messages)
+  open_inline_downloads  DecryptKey, then Decrypt under the keys it produced,
+                         which never leave the device
 """
 from __future__ import annotations
 
@@ -30,7 +38,8 @@ from typing import Dict, List, NamedTuple, Sequence, Tuple
 from . import _native as N
 from .ecclient import calc_padded
 from .eestream import SegmentCodec, _raise
-from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, DecryptionFailed, open_ranges_sized, open_segments_sized
+from .encryption import (DEFAULT_BLOCK_SIZE, TAG_SIZE, DecryptionFailed, KeyDecryptionFailed, device_rows,
+                         open_messages, open_ranges_sized, open_segments_sized)
 from .streams import calc_encompassing_blocks
 
 
@@ -322,6 +331,83 @@ def download_ranges(scheme, ranges: Sequence[Tuple[RangeGeometry, Dict[int, obje
     encs = decode_ranges(scheme, ranges, error_detection=error_detection, stream=stream)
     return open_ranges(scheme, [(g, e) for (g, _), e in zip(ranges, encs)], dev_keys, dev_nonces,
                        block_size=block_size, check=check, stream=stream)
+
+
+def open_content_keys(scheme, encrypted_keys, derived_keys, key_nonces, *, stream=None):
+    """encryption.DecryptKey (streams/store.go:349) for a batch: encrypted_keys
+    is [N, 48], derived_keys [N, 32], key_nonces [N, 12] -- device tensors, or N
+    byte strings each (nonces cut to their first 12 bytes).  Returns (keys,
+    status): keys the [N, 32] device tensor of content keys and status the [N]
+    int32 device tensor, 0, or 1 where the key did not verify (its row is then
+    zeros).  Asynchronous on `stream`."""
+    import torch
+
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        ek = device_rows(encrypted_keys, 48)
+        dk, kn = device_rows(derived_keys, 32, ek.device), device_rows(key_nonces, 12, ek.device)
+        n = len(ek)
+        if not (len(dk) == len(kn) == n):
+            raise ValueError("one derived key and one key nonce per encrypted key")
+        keys = torch.empty((n, 32), dtype=torch.uint8, device=ek.device)
+        status = torch.empty(n, dtype=torch.int32, device=ek.device)
+        if n:
+            open_messages(scheme, [ek.data_ptr() + 48 * g for g in range(n)], [32] * n, dk, kn,
+                          [keys.data_ptr() + 32 * g for g in range(n)], status, stream=stream)
+    return keys, status
+
+
+def open_inline_downloads(scheme, ciphers: Sequence[object], encrypted_keys, derived_keys, key_nonces, start_nonces, *,
+                          stream=None):
+    """decryptRanger for inline segments (streams/store.go:349, then the
+    whole-segment branch :360-375), for a batch: download g's content key is
+    opened from encrypted_keys[g] under derived_keys[g] and key_nonces[g], and
+    its data (ciphers[g], a contiguous uint8 device tensor of plaintext size + 16
+    bytes) under that content key and start_nonces[g].  Two ec_gcm_open_messages
+    calls in stream order; the content keys the first produces are the key array
+    of the second and never leave the device.  Returns per download its
+    plaintext as a device tensor, or an exception instance instead:
+    KeyDecryptionFailed(0) when its content key did not verify, DecryptionFailed(0)
+    when the key did and the data did not (or is shorter than a tag).  An empty
+    cipher text gives an empty plaintext (Decrypt does not open an empty slice).
+    Waits for the two calls (the statuses are read back)."""
+    import torch
+
+    ciphers = list(ciphers)
+    n = len(ciphers)
+    for c in ciphers:
+        if c.dtype != torch.uint8 or not c.is_contiguous():
+            raise ValueError("a download's cipher text is a contiguous uint8 tensor")
+    keys, kstatus = open_content_keys(scheme, encrypted_keys, derived_keys, key_nonces, stream=stream)
+    dev = keys.device
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        sn = device_rows(start_nonces, 12, dev)
+        if not (len(keys) == len(sn) == n):
+            raise ValueError("one encrypted key, derived key, key nonce and starting nonce per download")
+        data = [g for g, c in enumerate(ciphers) if c.numel() >= TAG_SIZE]
+        plains = [torch.empty(max(c.numel() - TAG_SIZE, 0), dtype=torch.uint8, device=dev) for c in ciphers]
+        dstatus = torch.zeros(max(len(data), 1), dtype=torch.int32, device=dev)
+        if data:
+            if len(data) == n:
+                k32, n12 = keys, sn
+            else:
+                idx = torch.tensor(data, dtype=torch.long, device=dev)
+                k32, n12 = keys[idx], sn[idx]
+            open_messages(scheme, [ciphers[g] for g in data], [ciphers[g].numel() - TAG_SIZE for g in data], k32, n12,
+                          [plains[g] if plains[g].numel() else None for g in data], dstatus, stream=stream)
+        if stream is not None and ts is None:  # a raw stream handle: not the stream the copies below run on
+            torch.cuda.synchronize()
+        kst, dst = kstatus.cpu().tolist(), dict(zip(data, dstatus.cpu().tolist()))
+    out: List[object] = []
+    for g, c in enumerate(ciphers):
+        if kst[g]:
+            out.append(KeyDecryptionFailed(0))
+        elif 0 < c.numel() < TAG_SIZE or dst.get(g, 0):
+            out.append(DecryptionFailed(0))
+        else:
+            out.append(plains[g])
+    return out
 
 
 class _Null:

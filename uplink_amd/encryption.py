@@ -11,6 +11,15 @@ Mirrors:
   AESGCMDecrypter/decrypt_segment  decryptRanger: NewDecrypter, Transform, Unpad
                                    streams/store.go:347-382
 
+  encrypt / decrypt                encryption.Encrypt / Decrypt for EncAESGCM: one whole
+                                   message, aesgcm.Seal(nil, nonce[:12], data, nil) -- the
+                                   inline segment (splitter.go:189, store.go:360-375),
+                                   stream info and ETags (uploader.go:421,438)
+  encrypt_key / decrypt_key        encryption.EncryptKey / DecryptKey: a 32-byte key
+                                   sealed to 48 bytes (splitter.go:160, store.go:349)
+  seal_messages / open_messages    lists of such messages, a raw key each, in one call
+                                   (ec_gcm_seal_messages / ec_gcm_open_messages)
+
 Every block is sealed or opened by the GPU (ec_gcm_*); a block whose tag
 does not verify raises DecryptionFailed ("cipher: message authentication
 failed", Go's crypto/cipher error) naming the block.
@@ -18,6 +27,7 @@ failed", Go's crypto/cipher error) naming the block.
 from __future__ import annotations
 
 import ctypes
+import threading
 
 import numpy as np
 
@@ -32,6 +42,12 @@ class DecryptionFailed(Exception):
     def __init__(self, block: int):
         super().__init__(f"cipher: message authentication failed (block {block})")
         self.block = block
+
+
+class KeyDecryptionFailed(DecryptionFailed):
+    """DecryptKey failed: the encrypted content key did not verify under the
+    derived key (downloads.open_inline_downloads tells it from a failure of the
+    data under a good content key, which is a plain DecryptionFailed)."""
 
 
 def increment(nonce: bytes, amount: int) -> bytes:
@@ -229,3 +245,145 @@ def open_segments(cipher, nseg: int, nblocks: int, in_block: int, dev_keys, dev_
     rc = N.load().ec_gcm_open_segments(C._addr(cipher), nseg, nblocks, in_block, C._addr(dev_keys),
                                        C._addr(dev_nonces), C._addr(out), C._addr(dev_status), C._stream(stream))
     _raise(None, rc)
+
+
+# ---- one-shot messages, a raw key each (ec_gcm_seal_messages / ec_gcm_open_messages) ----
+
+def _message_lists(what, bufs, lens, outs):
+    lens = [int(x) for x in lens]
+    bufs, outs = list(bufs), list(outs)
+    if len(bufs) != len(lens) or len(outs) != len(lens):
+        raise ValueError(f"one {what}, one length and one output per message")
+    if any(x < 0 for x in lens):
+        raise ValueError("a length is negative")
+    from .eestream import SegmentCodec as C
+    n = max(len(lens), 1)
+    c_in = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in bufs])
+    c_out = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in outs])
+    return len(lens), c_in, (ctypes.c_size_t * n)(*lens), c_out
+
+
+def seal_messages(scheme, plains, lens, dev_keys32, dev_nonces, outs, stream=None):
+    """ec_gcm_seal_messages: message i is lens[i] plaintext bytes at plains[i]
+    sealed under the 32 raw key bytes dev_keys32[32*i:] and the nonce
+    dev_nonces[12*i:] (device memory, any alignment) to lens[i]+16 bytes,
+    ciphertext || tag, at outs[i].  Entries are tensors, addresses or None (the
+    plaintext of an empty message); any alignment.  No prepared keys: the GPU
+    derives everything from the key bytes.  `scheme` supplies the device and
+    the staging.  Asynchronous on `stream`."""
+    from .eestream import SegmentCodec as C
+    nmsg, c_in, c_len, c_out = _message_lists("plaintext", plains, lens, outs)
+    rc = N.load().ec_gcm_seal_messages(scheme.ctx, nmsg, c_in, c_len, C._addr(dev_keys32), C._addr(dev_nonces), c_out,
+                                       C._stream(stream))
+    _raise(scheme.ctx, rc)
+
+
+def open_messages(scheme, ciphers, lens, dev_keys32, dev_nonces, outs, dev_status, stream=None):
+    """ec_gcm_open_messages: ciphers[i] is lens[i]+16 bytes, outs[i] lens[i]
+    (lens are plaintext lengths); dev_status is [nmsg] int32 on the device and
+    dev_status[i] ends as 0, or as 1 when the tag did not verify -- outs[i] is
+    then lens[i] zero bytes."""
+    from .eestream import SegmentCodec as C
+    nmsg, c_in, c_len, c_out = _message_lists("ciphertext", ciphers, lens, outs)
+    rc = N.load().ec_gcm_open_messages(scheme.ctx, nmsg, c_in, c_len, C._addr(dev_keys32), C._addr(dev_nonces), c_out,
+                                       C._addr(dev_status), C._stream(stream))
+    _raise(scheme.ctx, rc)
+
+
+class _MessageScheme:
+    """the context the bytes-in, bytes-out mirrors below run on (the message
+    calls take only the device and a staging pool from it); made on first use"""
+    _lock = threading.Lock()
+    _one = None
+
+    def __init__(self):
+        self.ctx = ctypes.c_void_p()
+        _raise(None, N.load().ec_create(2, 4, 16, ctypes.byref(self.ctx)))
+
+    @classmethod
+    def get(cls):
+        with cls._lock:
+            if cls._one is None:
+                cls._one = cls()
+            return cls._one
+
+
+def _one_message(data: bytes, key, nonce, open_: bool):
+    """one message through the GPU: the sealed bytes, or (plaintext, status)"""
+    import torch
+    key, nonce = _key(key), bytes(nonce)[:12]
+    if len(nonce) != 12:
+        raise ValueError("AES-256-GCM needs a nonce of at least 12 bytes")
+    n = len(data) - TAG_SIZE if open_ else len(data)
+    host = np.frombuffer(key + nonce + bytes(data), dtype=np.uint8).copy()
+    dev = torch.from_numpy(host).cuda()
+    out = torch.empty(max(n + (0 if open_ else TAG_SIZE), 1), dtype=torch.uint8, device=dev.device)
+    sch = _MessageScheme.get()
+    if not open_:
+        seal_messages(sch, [dev[44:] if n else None], [n], dev, dev[32:], [out])
+        return out.cpu().numpy()[:n + TAG_SIZE].tobytes()
+    status = torch.empty(1, dtype=torch.int32, device=dev.device)
+    open_messages(sch, [dev[44:]], [n], dev, dev[32:], [out if n else None], status)
+    return out.cpu().numpy()[:n].tobytes(), int(status.cpu()[0])
+
+
+def encrypt(data, key, nonce) -> bytes:
+    """encryption.Encrypt(data, EncAESGCM, key, nonce): the whole of `data` as
+    one GCM message under the first 12 bytes of `nonce`, ciphertext || tag, on
+    the GPU.  Empty data gives empty bytes without calling the cipher: that is
+    storj.io/common's rule ("don't encrypt empty slice"), stated here from
+    memory -- the module is a dependency of the reference, not part of it.
+    (ec_gcm_seal_messages itself treats length 0 as a message, as the GCM
+    specification's test case 13 does.)"""
+    data = bytes(data)
+    if not data:
+        return b""
+    return _one_message(data, key, nonce, False)
+
+
+def decrypt(cipher, key, nonce) -> bytes:
+    """encryption.Decrypt(cipher, EncAESGCM, key, nonce).  Raises
+    DecryptionFailed(0) when the tag does not verify, and for a cipher text
+    shorter than the 16-byte tag; empty input gives empty bytes (the rule of
+    encrypt, from memory as there)."""
+    cipher = bytes(cipher)
+    if not cipher:
+        return b""
+    if len(cipher) < TAG_SIZE:
+        raise DecryptionFailed(0)
+    plain, status = _one_message(cipher, key, nonce, True)
+    if status != 0:
+        raise DecryptionFailed(0)
+    return plain
+
+
+def encrypt_key(key_to_encrypt, key, nonce) -> bytes:
+    """encryption.EncryptKey(keyToEncrypt, EncAESGCM, key, nonce): the 32-byte
+    key sealed to 48 bytes (splitter.go:160)."""
+    return encrypt(_key(key_to_encrypt), key, nonce)
+
+
+def decrypt_key(encrypted, key, nonce) -> bytes:
+    """encryption.DecryptKey(encrypted, EncAESGCM, key, nonce) (store.go:349):
+    the 32-byte key, DecryptionFailed(0) when it does not verify."""
+    plain = decrypt(encrypted, key, nonce)
+    if len(plain) != 32:
+        raise ValueError("an encrypted key is 48 bytes")
+    return plain
+
+
+def device_rows(rows, width: int, device=None):
+    """[N, width] uint8 on the device from a device tensor of that shape or from
+    N byte strings, each cut to its first `width` bytes (a storj.Nonce is 24
+    bytes, AES-GCM takes 12)"""
+    import torch
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != width or not rows.is_contiguous():
+            raise ValueError(f"expected a contiguous [N, {width}] uint8 tensor")
+        return rows
+    rows = [bytes(r)[:width] for r in rows]
+    if any(len(r) != width for r in rows):
+        raise ValueError(f"expected {width} bytes per entry")
+    host = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), width).copy()
+    t = torch.from_numpy(host)
+    return t.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))

@@ -15,13 +15,16 @@ stream-ordered pass on the GPU.
   cipher_geometry   (nblocks, plain_cap, enc_len) of an upload through the cipher
   seal_uploads      the encrypted segments of a batch of uploads, each in the
                     buffer encode_uploads takes (ec_gcm_seal_segments_sized)
+  seal_inline_uploads  the encrypted inline data and encrypted content keys of a
+                    batch of uploads too small to be erasure coded
+                    (ec_gcm_seal_messages)
 """
 from __future__ import annotations
 
 from typing import Sequence, Tuple
 
 from .eestream import SegmentCodec
-from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, seal_segments_sized
+from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, device_rows, seal_messages, seal_segments_sized
 
 
 def upload_geometry(size: int, es) -> Tuple[int, int, int]:
@@ -123,6 +126,56 @@ def seal_uploads(scheme, uploads: Sequence[Tuple[int, object]], dev_keys, dev_no
         seal_segments_sized(scheme, [g[3] for g in geo], [g[1] for g in geo], block_size - TAG_SIZE, dev_keys,
                             dev_nonces, encs, data_len=[g[0] for g in geo], stream=stream)
     return [(g[2], e) for g, e in zip(geo, encs)]
+
+
+def seal_inline_uploads(scheme, uploads: Sequence[object], content_keys, nonces, derived_keys, key_nonces, *,
+                        stream=None):
+    """What the splitter does for an object of up to maxInlineSize bytes
+    (splitter/splitter.go:160,189), for a batch: upload g's plaintext
+    (uploads[g], a contiguous uint8 device tensor) is sealed whole under its
+    content key and nonce -- encryption.Encrypt(inline, cipher, &contentKey,
+    &nonce) --, and its content key under its derived key and key nonce --
+    encryption.EncryptKey(&contentKey, cipher, key, &keyNonce).  One
+    ec_gcm_seal_messages call over the 2N messages.  content_keys and
+    derived_keys are [N, 32], nonces and key_nonces [N, 12]: device tensors, or
+    N byte strings each (nonces cut to their first 12 bytes).  Returns
+    (encrypted, encrypted_keys): encrypted[g] is the device tensor of upload g's
+    size + 16 bytes (empty for an empty upload: Encrypt does not seal an empty
+    slice) and encrypted_keys the [N, 48] device tensor.  Asynchronous on
+    `stream`."""
+    import torch
+
+    uploads = list(uploads)
+    n = len(uploads)
+    for buf in uploads:
+        if buf.dtype != torch.uint8 or not buf.is_contiguous():
+            raise ValueError("an upload's plaintext is a contiguous uint8 tensor")
+    dev = uploads[0].device if uploads else torch.device("cuda", torch.cuda.current_device())
+    ts = stream if hasattr(stream, "cuda_stream") else None
+    with torch.cuda.stream(ts) if ts is not None else _Null():
+        ck, dk = device_rows(content_keys, 32, dev), device_rows(derived_keys, 32, dev)
+        nn, kn = device_rows(nonces, 12, dev), device_rows(key_nonces, 12, dev)
+        if not (len(ck) == len(dk) == len(nn) == len(kn) == n):
+            raise ValueError("one content key, nonce, derived key and key nonce per upload")
+        encs = [torch.empty(b.numel() + TAG_SIZE if b.numel() else 0, dtype=torch.uint8, device=dev) for b in uploads]
+        enc_keys = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return encs, enc_keys
+        data = [g for g, b in enumerate(uploads) if b.numel()]  # (an empty upload is not a message)
+        if len(data) == n:
+            keys32, nonces12 = torch.cat([ck, dk]), torch.cat([nn, kn])
+        else:
+            idx = torch.tensor(data, dtype=torch.long, device=dev)
+            keys32, nonces12 = torch.cat([ck[idx], dk]), torch.cat([nn[idx], kn])
+        plains = [uploads[g] for g in data] + [ck.data_ptr() + 32 * g for g in range(n)]
+        outs = [encs[g] for g in data] + [enc_keys.data_ptr() + 48 * g for g in range(n)]
+        lens = [uploads[g].numel() for g in data] + [32] * n
+        seal_messages(scheme, plains, lens, keys32, nonces12, outs, stream=stream)
+        # keys32 and nonces12 are read by the queued kernels: freed on this stream they are reused only
+        # behind them; a raw stream handle is not the stream they were made on, so wait for it
+        if stream is not None and ts is None:
+            torch.cuda.synchronize()
+    return encs, enc_keys
 
 
 class _Null:
