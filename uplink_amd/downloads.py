@@ -35,6 +35,7 @@ from __future__ import annotations
 
 from typing import Dict, List, NamedTuple, Sequence, Tuple
 
+from . import _batch as B
 from . import _native as N
 from .ecclient import calc_padded
 from .eestream import SegmentCodec, _raise
@@ -61,6 +62,39 @@ def _error_of(ctx, code: int):
     return None
 
 
+def _decode(scheme, sets, nstripes, out_sizes, error_detection, collect_errors, stream):
+    """The decode behind decode_downloads and decode_ranges: one
+    rebuild_segments_sized (with error_detection, decode_segments_sized) call
+    over the share sets, a (nums, piece tensors) and a stripe count per
+    segment.  Returns (outputs, errors): segment g's out_sizes[g] decoded bytes
+    and its eestream exception or None."""
+    import torch
+
+    codec = SegmentCodec(scheme)
+    dev = next((p.device for _, pieces in sets for p in pieces), None)
+    if dev is None:
+        dev = B.default_device()
+    with B.stream_scope(stream):
+        # one allocation per output: each is 16-byte aligned, so every segment stays in the pass
+        outs = [torch.empty(n, dtype=torch.uint8, device=dev) for n in out_sizes]
+        ptrs = [o if o.numel() else None for o in outs]
+        errors: List[object] = [None] * len(outs)
+        if error_detection:
+            codes = codec.decode_segments_sized(sets, nstripes, ptrs, stream=stream, collect=collect_errors)
+            errors = [_error_of(scheme.ctx, c) for c in codes]
+        else:
+            codec.rebuild_segments_sized(sets, nstripes, ptrs, stream=stream)
+    return outs, errors
+
+
+def _share_set(ctx, pieces: Dict[int, object], piece_size: int):
+    """(nums, piece tensors) of the pieces that arrived, each piece_size bytes"""
+    nums = list(pieces.keys())
+    if any(pieces[x].numel() != piece_size for x in nums):
+        _raise(ctx, N.EC_ERR_SHARE_SIZE)
+    return nums, [pieces[x] for x in nums]
+
+
 def decode_downloads(scheme, downloads: Sequence[Tuple[int, Dict[int, object]]], *, error_detection: bool = False,
                      collect_errors: bool = False, stream=None):
     """downloads: per download (size, {piece number: uint8 device tensor}), the
@@ -76,38 +110,24 @@ def decode_downloads(scheme, downloads: Sequence[Tuple[int, Dict[int, object]]],
     return value is (outputs, errors): a segment that failed has its eestream
     exception in `errors` (None for the others) instead of raising, and its
     output is not to be used."""
-    import torch
-
-    codec = SegmentCodec(scheme)
-    ctx = scheme.ctx
     sets, nstripes, geo = [], [], []
-    dev = None
     for size, pieces in downloads:
         padded, piece_size, ns = segment_geometry(int(size), scheme)
-        nums = list(pieces.keys())
-        for x in nums:
-            if pieces[x].numel() != piece_size:
-                _raise(ctx, N.EC_ERR_SHARE_SIZE)
-            if dev is None:
-                dev = pieces[x].device
-        sets.append((nums, [pieces[x] for x in nums]))
+        sets.append(_share_set(scheme.ctx, pieces, piece_size))
         nstripes.append(ns)
         geo.append((int(size), padded))
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
-        # one allocation per output: each is 16-byte aligned, so every segment stays in the pass
-        outs = [torch.empty(padded, dtype=torch.uint8, device=dev) for _, padded in geo]
-        ptrs = [o if o.numel() else None for o in outs]
-        errors: List[object] = [None] * len(outs)
-        if error_detection:
-            codes = codec.decode_segments_sized(sets, nstripes, ptrs, stream=stream, collect=collect_errors)
-            errors = [_error_of(ctx, c) for c in codes]
-        else:
-            codec.rebuild_segments_sized(sets, nstripes, ptrs, stream=stream)
+    outs, errors = _decode(scheme, sets, nstripes, [padded for _, padded in geo], error_detection, collect_errors,
+                           stream)
     res = [o[:size] for o, (size, _) in zip(outs, geo)]
     return (res, errors) if collect_errors else res
+
+
+def _raise_first_failure(status, stream):
+    """check=True of the opens: waits for `stream` and raises
+    DecryptionFailed(block) for the first download whose status names a block"""
+    for block in B.read_back(status, stream):
+        if block >= 0:
+            raise DecryptionFailed(block)
 
 
 def open_downloads(scheme, sealed: Sequence[Tuple[int, object]], dev_keys, dev_nonces, *,
@@ -128,31 +148,22 @@ def open_downloads(scheme, sealed: Sequence[Tuple[int, object]], dev_keys, dev_n
     from .uploads import cipher_geometry
 
     geo = []
-    dev = None
     for size, enc in sealed:
         nblocks, plain_cap, enc_len = cipher_geometry(int(size), block_size)
         if enc.dtype != torch.uint8 or not enc.is_contiguous():
             raise ValueError("a download's encrypted segment is a contiguous uint8 tensor")
         if enc.numel() != enc_len:
             raise ValueError(f"a download of {int(size)} bytes has {enc_len} encrypted bytes, got {enc.numel()}")
-        if dev is None:
-            dev = enc.device
         geo.append((int(size), nblocks, plain_cap, enc))
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    dev = geo[0][3].device if geo else B.default_device()
+    with B.stream_scope(stream):
         outs = [torch.empty(g[2], dtype=torch.uint8, device=dev) for g in geo]
         status = torch.empty(len(geo), dtype=torch.int32, device=dev)
         if geo:
             open_segments_sized(scheme, [g[3] for g in geo], [g[1] for g in geo], block_size - TAG_SIZE, dev_keys,
                                 dev_nonces, outs, status, stream=stream)
         if check:
-            if stream is not None and ts is None:  # a raw stream handle: not the stream the copy below runs on
-                torch.cuda.synchronize()
-            for block in status.cpu().tolist():  # (a copy on the current stream: it waits for the open)
-                if block >= 0:
-                    raise DecryptionFailed(block)
+            _raise_first_failure(status, stream)
     return [o[:g[0]] for o, g in zip(outs, geo)], status
 
 
@@ -244,35 +255,11 @@ def decode_ranges(scheme, ranges: Sequence[Tuple[RangeGeometry, Dict[int, object
     decoded stripes: the covered cipher blocks, as open_ranges takes them.  A
     piece of another length raises as EC_ERR_SHARE_SIZE does; error_detection
     and collect_errors are decode_downloads'."""
-    import torch
-
-    codec = SegmentCodec(scheme)
-    ctx = scheme.ctx
     stripe = scheme.stripe_size()
-    sets, nstripes, geos = [], [], []
-    dev = None
-    for geo, pieces in ranges:
-        nums = list(pieces.keys())
-        for x in nums:
-            if pieces[x].numel() != geo.piece_length:
-                _raise(ctx, N.EC_ERR_SHARE_SIZE)
-            if dev is None:
-                dev = pieces[x].device
-        sets.append((nums, [pieces[x] for x in nums]))
-        nstripes.append(geo.nstripes)
-        geos.append(geo)
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
-        outs = [torch.empty(g.nstripes * stripe, dtype=torch.uint8, device=dev) for g in geos]
-        ptrs = [o if o.numel() else None for o in outs]
-        errors: List[object] = [None] * len(outs)
-        if error_detection:
-            codes = codec.decode_segments_sized(sets, nstripes, ptrs, stream=stream, collect=collect_errors)
-            errors = [_error_of(ctx, c) for c in codes]
-        else:
-            codec.rebuild_segments_sized(sets, nstripes, ptrs, stream=stream)
+    geos = [g for g, _ in ranges]
+    sets = [_share_set(scheme.ctx, pieces, g.piece_length) for g, pieces in ranges]
+    outs, errors = _decode(scheme, sets, [g.nstripes for g in geos], [g.nstripes * stripe for g in geos],
+                           error_detection, collect_errors, stream)
     res = [o[g.skip:g.skip + g.enc_length] for o, g in zip(outs, geos)]
     return (res, errors) if collect_errors else res
 
@@ -293,20 +280,15 @@ def open_ranges(scheme, sealed: Sequence[Tuple[RangeGeometry, object]], dev_keys
     import torch
 
     ib = int(block_size) - TAG_SIZE
-    dev = None
     for geo, enc in sealed:
         if enc.dtype != torch.uint8 or not enc.is_contiguous():
             raise ValueError("a download's covered blocks are a contiguous uint8 tensor")
         if enc.numel() != geo.enc_length or geo.enc_length != geo.nblocks * int(block_size):
             raise ValueError(f"a range of {geo.nblocks} blocks has {geo.nblocks * int(block_size)} encrypted bytes, "
                              f"got {enc.numel()}")
-        if dev is None:
-            dev = enc.device
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
     geos = [g for g, _ in sealed]
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    dev = sealed[0][1].device if geos else B.default_device()
+    with B.stream_scope(stream):
         outs = [torch.empty(g.length, dtype=torch.uint8, device=dev) for g in geos]
         status = torch.empty(len(geos), dtype=torch.int32, device=dev)
         if geos:
@@ -314,11 +296,7 @@ def open_ranges(scheme, sealed: Sequence[Tuple[RangeGeometry, object]], dev_keys
                               [g.nblocks for g in geos], [g.head for g in geos], [g.length for g in geos], ib, dev_keys,
                               dev_nonces, [o if o.numel() else None for o in outs], status, stream=stream)
         if check:
-            if stream is not None and ts is None:  # a raw stream handle: not the stream the copy below runs on
-                torch.cuda.synchronize()
-            for block in status.cpu().tolist():  # (a copy on the current stream: it waits for the open)
-                if block >= 0:
-                    raise DecryptionFailed(block)
+            _raise_first_failure(status, stream)
     return outs, status
 
 
@@ -342,8 +320,7 @@ def open_content_keys(scheme, encrypted_keys, derived_keys, key_nonces, *, strea
     zeros).  Asynchronous on `stream`."""
     import torch
 
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    with B.stream_scope(stream):
         ek = device_rows(encrypted_keys, 48)
         dk, kn = device_rows(derived_keys, 32, ek.device), device_rows(key_nonces, 12, ek.device)
         n = len(ek)
@@ -380,8 +357,7 @@ def open_inline_downloads(scheme, ciphers: Sequence[object], encrypted_keys, der
             raise ValueError("a download's cipher text is a contiguous uint8 tensor")
     keys, kstatus = open_content_keys(scheme, encrypted_keys, derived_keys, key_nonces, stream=stream)
     dev = keys.device
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    with B.stream_scope(stream):
         sn = device_rows(start_nonces, 12, dev)
         if not (len(keys) == len(sn) == n):
             raise ValueError("one encrypted key, derived key, key nonce and starting nonce per download")
@@ -396,9 +372,7 @@ def open_inline_downloads(scheme, ciphers: Sequence[object], encrypted_keys, der
                 k32, n12 = keys[idx], sn[idx]
             open_messages(scheme, [ciphers[g] for g in data], [ciphers[g].numel() - TAG_SIZE for g in data], k32, n12,
                           [plains[g] if plains[g].numel() else None for g in data], dstatus, stream=stream)
-        if stream is not None and ts is None:  # a raw stream handle: not the stream the copies below run on
-            torch.cuda.synchronize()
-        kst, dst = kstatus.cpu().tolist(), dict(zip(data, dstatus.cpu().tolist()))
+        kst, dst = B.read_back(kstatus, stream), dict(zip(data, B.read_back(dstatus, stream)))
     out: List[object] = []
     for g, c in enumerate(ciphers):
         if kst[g]:
@@ -408,11 +382,3 @@ def open_inline_downloads(scheme, ciphers: Sequence[object], encrypted_keys, der
         else:
             out.append(plains[g])
     return out
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False

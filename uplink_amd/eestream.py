@@ -31,6 +31,7 @@ from typing import Callable, Iterable, List, Optional
 
 import numpy as np
 
+from . import _batch as B
 from . import _native as N
 
 
@@ -458,24 +459,14 @@ class SegmentCodec:
         self.scheme = scheme
         self._lib = scheme._lib
 
-    @staticmethod
-    def _addr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
-    @staticmethod
-    def _stream(stream):
-        if stream is None:
-            try:
-                import torch
-                return torch.cuda.current_stream().cuda_stream
-            except Exception:
-                return None
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    # (kept under these names for pipeline-style callers outside the package)
+    _addr = staticmethod(B.addr)
+    _stream = staticmethod(B.stream_handle)
 
     def encode_segments(self, segs, nseg: int, nstripes: int, pieces, parity_only: bool = False, stream=None):
         flags = N.EC_FLAG_PARITY_ONLY if parity_only else 0
-        rc = self._lib.ec_encode_segments(self.scheme.ctx, self._addr(segs), nseg, nstripes, self._addr(pieces),
-                                          flags, self._stream(stream))
+        rc = self._lib.ec_encode_segments(self.scheme.ctx, B.addr(segs), nseg, nstripes, B.addr(pieces), flags,
+                                          B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
 
     def encode_segments_sized(self, segs, nstripes, pieces, data_len=None, parity_only: bool = False, stream=None):
@@ -487,24 +478,15 @@ class SegmentCodec:
         data_len[g] bytes and PadReader's padding is written behind them before
         the encode.  nstripes[g] == 0 skips segment g (its buffers may be None).
         Asynchronous on `stream`."""
-        nstripes = [int(x) for x in nstripes]
-        segs, pieces = list(segs), list(pieces)
-        if len(segs) != len(nstripes) or len(pieces) != len(nstripes):
-            raise ValueError("one segment, one stripe count and one piece buffer per segment")
-        if any(x < 0 for x in nstripes):
-            raise ValueError("a stripe count is negative")
+        nstripes, segs, pieces = list(nstripes), list(segs), list(pieces)
         nseg = len(nstripes)
-        c_len = None
-        if data_len is not None:
-            data_len = [int(x) for x in data_len]
-            if len(data_len) != nseg or any(x < 0 for x in data_len):
-                raise ValueError("one non-negative data length per segment")
-            c_len = (ctypes.c_size_t * max(nseg, 1))(*data_len)
-        c_segs = (ctypes.c_void_p * max(nseg, 1))(*[0 if x is None else self._addr(x) for x in segs])
-        c_out = (ctypes.c_void_p * max(nseg, 1))(*[0 if x is None else self._addr(x) for x in pieces])
-        rc = self._lib.ec_encode_segments_sized(self.scheme.ctx, nseg, c_segs, (ctypes.c_size_t * max(nseg, 1))(*nstripes),
-                                                c_len, c_out, N.EC_FLAG_PARITY_ONLY if parity_only else 0,
-                                                self._stream(stream))
+        if len(segs) != nseg or len(pieces) != nseg:
+            raise ValueError("one segment, one stripe count and one piece buffer per segment")
+        c_nst = B.size_array(nstripes, nseg, "stripe count")
+        c_len = None if data_len is None else B.size_array(data_len, nseg, "data length", one_error=True)
+        rc = self._lib.ec_encode_segments_sized(self.scheme.ctx, nseg, B.ptr_array(segs), c_nst, c_len,
+                                                B.ptr_array(pieces), N.EC_FLAG_PARITY_ONLY if parity_only else 0,
+                                                B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
 
     def hash_segments_sized(self, segs, nstripes, pieces, hashes, parity_only: bool = False, stream=None, algo=None):
@@ -520,49 +502,44 @@ class SegmentCodec:
         piecehash.hash_segments_sized(self.scheme, segs, nstripes, pieces, hashes, parity_only=parity_only,
                                       stream=stream, algo=piecehash.DEFAULT_ALGORITHM if algo is None else algo)
 
+    @staticmethod
+    def _one_set_args(nums, piece_ptrs):
+        """(nshares, nums[], piece pointers[]) of the batched exports: one share set for every segment"""
+        nums, ptrs = list(nums), list(piece_ptrs)
+        if len(ptrs) != len(nums):
+            raise ValueError("nums and piece pointers differ in length")
+        return len(nums), B.int_array(nums), B.ptr_array(ptrs)
+
     def decode_segments(self, nums: Iterable[int], piece_ptrs: Iterable[int], nstripes: int, out, nseg: int = 1,
                         piece_seg_stride: int = 0, out_seg_stride: int = 0, stream=None):
         """Decode (Correct + Rebuild) of a whole segment's pieces on the device
         (ec_decode_segments; StripeReader with error detection, stripe.go:407-408):
         corrected shares are written back into the pieces; returns when done."""
-        nums = list(nums)
-        ptrs = [self._addr(p) for p in piece_ptrs]
-        if len(ptrs) != len(nums):
-            raise ValueError("nums and piece pointers differ in length")
-        c_nums = (ctypes.c_int * max(len(nums), 1))(*nums)
-        c_ptrs = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
-        rc = self._lib.ec_decode_segments_batched(self.scheme.ctx, len(nums), c_nums, c_ptrs, nstripes, nseg,
-                                                  piece_seg_stride, out_seg_stride, self._addr(out),
-                                                  self._stream(stream))
+        rc = self._lib.ec_decode_segments_batched(self.scheme.ctx, *self._one_set_args(nums, piece_ptrs), nstripes, nseg,
+                                                  piece_seg_stride, out_seg_stride, B.addr(out),
+                                                  B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
 
     def rebuild_segments(self, nums: Iterable[int], piece_ptrs: Iterable[int], nstripes: int, out, nseg: int = 1,
                          piece_seg_stride: int = 0, out_seg_stride: int = 0, stream=None):
-        nums = list(nums)
-        ptrs = [self._addr(p) for p in piece_ptrs]
-        if len(ptrs) != len(nums):
-            raise ValueError("nums and piece pointers differ in length")
-        c_nums = (ctypes.c_int * max(len(nums), 1))(*nums)
-        c_ptrs = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
-        rc = self._lib.ec_rebuild_segments_batched(self.scheme.ctx, len(nums), c_nums, c_ptrs, nstripes, nseg,
-                                                   piece_seg_stride, out_seg_stride, self._addr(out),
-                                                   self._stream(stream))
+        rc = self._lib.ec_rebuild_segments_batched(self.scheme.ctx, *self._one_set_args(nums, piece_ptrs), nstripes, nseg,
+                                                   piece_seg_stride, out_seg_stride, B.addr(out),
+                                                   B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
 
-    def _sets_args(self, sets, outs):
-        sets = [(list(nums), [self._addr(p) for p in ptrs]) for nums, ptrs in sets]
-        outs = [self._addr(o) for o in outs]
-        if len(outs) != len(sets):
-            raise ValueError("one output per segment")
+    def _sets_args(self, sets, outs, nstripes=None):
+        """(nseg, nshares[], nums[], piece pointers[], outputs[]) of a share
+        set per segment; with nstripes also the size_t array of a stripe count
+        per segment (the _sized exports)"""
+        nst = None if nstripes is None else B.size_array(nstripes, len(sets), "stripe count")
+        sets = [(list(nums), list(ptrs)) for nums, ptrs in sets]
+        optr = B.ptr_array(outs, len(sets), "output")  # (a skipped segment's output may be None)
         for nums, ptrs in sets:
             if len(nums) != len(ptrs):
                 raise ValueError("nums and piece pointers differ in length")
-        nseg = len(sets)
-        flat_n = [x for nums, _ in sets for x in nums]
-        flat_p = [x for _, ptrs in sets for x in ptrs]
-        return (nseg, (ctypes.c_int * max(nseg, 1))(*[len(nums) for nums, _ in sets]),
-                (ctypes.c_int * max(len(flat_n), 1))(*flat_n), (ctypes.c_void_p * max(len(flat_p), 1))(*flat_p),
-                (ctypes.c_void_p * max(nseg, 1))(*outs))
+        args = (len(sets), B.int_array([len(nums) for nums, _ in sets]), B.int_array([x for nums, _ in sets for x in nums]),
+                B.ptr_array([x for _, ptrs in sets for x in ptrs]), optr)
+        return args if nstripes is None else args + (nst,)
 
     def rebuild_segments_sets(self, sets, nstripes: int, outs, stream=None):
         """Rebuild of many segments, each from a share set of its own, in one
@@ -572,7 +549,7 @@ class SegmentCodec:
         under prefetch (store.go:240-253).  Asynchronous on `stream`."""
         nseg, nsh, nums, ptrs, optr = self._sets_args(sets, outs)
         rc = self._lib.ec_rebuild_segments_sets(self.scheme.ctx, nseg, nsh, nums, ptrs, nstripes, optr,
-                                                self._stream(stream))
+                                                B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
 
     def decode_segments_sets(self, sets, nstripes: int, outs, stream=None):
@@ -582,27 +559,17 @@ class SegmentCodec:
         done."""
         nseg, nsh, nums, ptrs, optr = self._sets_args(sets, outs)
         rc = self._lib.ec_decode_segments_sets(self.scheme.ctx, nseg, nsh, nums, ptrs, nstripes, optr,
-                                               self._stream(stream))
+                                               B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
-
-    def _sized_args(self, sets, nstripes, outs):
-        nstripes = [int(x) for x in nstripes]
-        if len(nstripes) != len(sets):
-            raise ValueError("one stripe count per segment")
-        if any(x < 0 for x in nstripes):
-            raise ValueError("a stripe count is negative")
-        # (a skipped segment's output may be None)
-        outs = [0 if o is None else o for o in outs]
-        return self._sets_args(sets, outs), (ctypes.c_size_t * max(len(nstripes), 1))(*nstripes)
 
     def rebuild_segments_sized(self, sets, nstripes, outs, stream=None):
         """rebuild_segments_sets with a stripe count per segment
         (ec_rebuild_segments_sized): the downloads in flight at once differ in
         size (client.go:302-303), and one stream-ordered pass serves them all.
         nstripes[g] == 0 skips segment g.  Asynchronous on `stream`."""
-        (nseg, nsh, nums, ptrs, optr), nst = self._sized_args(sets, nstripes, outs)
+        nseg, nsh, nums, ptrs, optr, nst = self._sets_args(sets, outs, nstripes)
         rc = self._lib.ec_rebuild_segments_sized(self.scheme.ctx, nseg, nsh, nums, ptrs, nst, optr,
-                                                 self._stream(stream))
+                                                 B.stream_handle(stream))
         _raise(self.scheme.ctx, rc)
 
     def decode_segments_sized(self, sets, nstripes, outs, stream=None, collect: bool = False):
@@ -611,10 +578,10 @@ class SegmentCodec:
         returns the per-segment codes (EC_OK, EC_ERR_TOO_MANY_ERRORS, ...) when
         done.  Unless `collect`, the first non-OK outcome raises as
         decode_segments_sets raises it."""
-        (nseg, nsh, nums, ptrs, optr), nst = self._sized_args(sets, nstripes, outs)
-        seg_rc = (ctypes.c_int * max(nseg, 1))()
+        nseg, nsh, nums, ptrs, optr, nst = self._sets_args(sets, outs, nstripes)
+        seg_rc = B.int_array([0] * nseg)
         rc = self._lib.ec_decode_segments_sized(self.scheme.ctx, nseg, nsh, nums, ptrs, nst, optr, seg_rc,
-                                                self._stream(stream))
+                                                B.stream_handle(stream))
         codes = [int(seg_rc[g]) for g in range(nseg)]
         # (an argument error is the call's, not a segment's: every code is still EC_OK)
         if rc != N.EC_OK and (not collect or all(x == N.EC_OK for x in codes)):

@@ -31,6 +31,7 @@ import threading
 
 import numpy as np
 
+from . import _batch as B
 from . import _native as N
 from .eestream import _raise, pad, unpad
 
@@ -149,14 +150,12 @@ def prepare_keys(keys, dev_buf=None, stream=None):
     """ec_gcm_prepare_keys into a device buffer (torch uint8 tensor allocated
     when dev_buf is None); returns it."""
     import torch
-    from .eestream import SegmentCodec
     keys = [_key(k) for k in keys]
     nbytes = len(keys) * N.load().ec_gcm_key_bytes()
     if dev_buf is None:
         dev_buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
     host = np.frombuffer(b"".join(keys), dtype=np.uint8)
-    rc = N.load().ec_gcm_prepare_keys(host.ctypes.data, len(keys), SegmentCodec._addr(dev_buf),
-                                      SegmentCodec._stream(stream))
+    rc = N.load().ec_gcm_prepare_keys(host.ctypes.data, len(keys), B.addr(dev_buf), B.stream_handle(stream))
     _raise(None, rc)
     return dev_buf
 
@@ -164,24 +163,19 @@ def prepare_keys(keys, dev_buf=None, stream=None):
 def seal_segments(plain, nseg: int, nblocks: int, in_block: int, dev_keys, dev_nonces, out, stream=None):
     """ec_gcm_seal_segments on device buffers: [nseg][nblocks*in_block] ->
     [nseg][nblocks*(in_block+16)]."""
-    from .eestream import SegmentCodec as C
-    rc = N.load().ec_gcm_seal_segments(C._addr(plain), nseg, nblocks, in_block, C._addr(dev_keys),
-                                       C._addr(dev_nonces), C._addr(out), C._stream(stream))
+    rc = N.load().ec_gcm_seal_segments(B.addr(plain), nseg, nblocks, in_block, B.addr(dev_keys), B.addr(dev_nonces),
+                                       B.addr(out), B.stream_handle(stream))
     _raise(None, rc)
 
 
-def _sized_lists(what, bufs, nblocks, outs):
-    nblocks = [int(x) for x in nblocks]
-    bufs, outs = list(bufs), list(outs)
-    if len(bufs) != len(nblocks) or len(outs) != len(nblocks):
-        raise ValueError(f"one {what}, one block count and one output per segment")
-    if any(x < 0 for x in nblocks):
-        raise ValueError("a block count is negative")
-    from .eestream import SegmentCodec as C
-    n = max(len(nblocks), 1)
-    c_in = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in bufs])
-    c_out = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in outs])
-    return len(nblocks), c_in, (ctypes.c_size_t * n)(*nblocks), c_out
+def _in_out_lists(what, bufs, count, sizes, outs, per):
+    """(n, inputs[], sizes[], outputs[]) of a call that takes one input, one
+    size (a `count`: "block count", "length") and one output per segment or message"""
+    bufs, sizes, outs = list(bufs), list(sizes), list(outs)
+    n = len(sizes)
+    if len(bufs) != n or len(outs) != n:
+        raise ValueError(f"one {what}, one {count} and one output per {per}")
+    return n, B.ptr_array(bufs), B.size_array(sizes, n, count), B.ptr_array(outs)
 
 
 def seal_segments_sized(scheme, plains, nblocks, in_block: int, dev_keys, dev_nonces, outs, data_len=None,
@@ -192,16 +186,10 @@ def seal_segments_sized(scheme, plains, nblocks, in_block: int, dev_keys, dev_no
     (a segment of 0 blocks).  With data_len, segment g holds data_len[g] bytes
     and PadReader's padding to in_block is written behind them before the seal.
     `scheme` supplies the device and the staging.  Asynchronous on `stream`."""
-    from .eestream import SegmentCodec as C
-    nseg, c_in, c_nb, c_out = _sized_lists("plaintext", plains, nblocks, outs)
-    c_len = None
-    if data_len is not None:
-        data_len = [int(x) for x in data_len]
-        if len(data_len) != nseg or any(x < 0 for x in data_len):
-            raise ValueError("one non-negative data length per segment")
-        c_len = (ctypes.c_size_t * max(nseg, 1))(*data_len)
-    rc = N.load().ec_gcm_seal_segments_sized(scheme.ctx, nseg, c_in, c_nb, c_len, int(in_block), C._addr(dev_keys),
-                                             C._addr(dev_nonces), c_out, C._stream(stream))
+    nseg, c_in, c_nb, c_out = _in_out_lists("plaintext", plains, "block count", nblocks, outs, "segment")
+    c_len = None if data_len is None else B.size_array(data_len, nseg, "data length", one_error=True)
+    rc = N.load().ec_gcm_seal_segments_sized(scheme.ctx, nseg, c_in, c_nb, c_len, int(in_block), B.addr(dev_keys),
+                                             B.addr(dev_nonces), c_out, B.stream_handle(stream))
     _raise(scheme.ctx, rc)
 
 
@@ -210,10 +198,9 @@ def open_segments_sized(scheme, ciphers, nblocks, in_block: int, dev_keys, dev_n
     """ec_gcm_open_segments_sized: ciphers[g] is nblocks[g]*(in_block+16) bytes,
     outs[g] nblocks[g]*in_block; dev_status is [nseg] int32 on the device and
     dev_status[g] ends as -1 or the first failing block of segment g."""
-    from .eestream import SegmentCodec as C
-    nseg, c_in, c_nb, c_out = _sized_lists("ciphertext", ciphers, nblocks, outs)
-    rc = N.load().ec_gcm_open_segments_sized(scheme.ctx, nseg, c_in, c_nb, int(in_block), C._addr(dev_keys),
-                                             C._addr(dev_nonces), c_out, C._addr(dev_status), C._stream(stream))
+    nseg, c_in, c_nb, c_out = _in_out_lists("ciphertext", ciphers, "block count", nblocks, outs, "segment")
+    rc = N.load().ec_gcm_open_segments_sized(scheme.ctx, nseg, c_in, c_nb, int(in_block), B.addr(dev_keys),
+                                             B.addr(dev_nonces), c_out, B.addr(dev_status), B.stream_handle(stream))
     _raise(scheme.ctx, rc)
 
 
@@ -224,44 +211,24 @@ def open_ranges_sized(scheme, ciphers, first_block, nblocks, head, length, in_bl
     length[g] plaintext bytes that start head[g] bytes into the first of them;
     any alignment.  dev_status[g] ends as -1 or the smallest absolute number of
     a covered block that failed."""
-    from .eestream import SegmentCodec as C
-    nseg, c_in, c_nb, c_out = _sized_lists("ciphertext", ciphers, nblocks, outs)
-    per = []
-    for name, v in (("first block", first_block), ("head", head), ("length", length)):
-        v = [int(x) for x in v]
-        if len(v) != nseg or any(x < 0 for x in v):
-            raise ValueError(f"one non-negative {name} per segment")
-        per.append((ctypes.c_size_t * max(nseg, 1))(*v))
-    rc = N.load().ec_gcm_open_ranges_sized(scheme.ctx, nseg, c_in, per[0], c_nb, per[1], per[2], int(in_block),
-                                           C._addr(dev_keys), C._addr(dev_nonces), c_out, C._addr(dev_status),
-                                           C._stream(stream))
+    nseg, c_in, c_nb, c_out = _in_out_lists("ciphertext", ciphers, "block count", nblocks, outs, "segment")
+    c_first, c_head, c_length = [B.size_array(v, nseg, noun, one_error=True)
+                                 for noun, v in (("first block", first_block), ("head", head), ("length", length))]
+    rc = N.load().ec_gcm_open_ranges_sized(scheme.ctx, nseg, c_in, c_first, c_nb, c_head, c_length, int(in_block),
+                                           B.addr(dev_keys), B.addr(dev_nonces), c_out, B.addr(dev_status),
+                                           B.stream_handle(stream))
     _raise(scheme.ctx, rc)
 
 
 def open_segments(cipher, nseg: int, nblocks: int, in_block: int, dev_keys, dev_nonces, out, dev_status,
                   stream=None):
     """ec_gcm_open_segments; dev_status[g] = -1 or the first failing block."""
-    from .eestream import SegmentCodec as C
-    rc = N.load().ec_gcm_open_segments(C._addr(cipher), nseg, nblocks, in_block, C._addr(dev_keys),
-                                       C._addr(dev_nonces), C._addr(out), C._addr(dev_status), C._stream(stream))
+    rc = N.load().ec_gcm_open_segments(B.addr(cipher), nseg, nblocks, in_block, B.addr(dev_keys), B.addr(dev_nonces),
+                                       B.addr(out), B.addr(dev_status), B.stream_handle(stream))
     _raise(None, rc)
 
 
 # ---- one-shot messages, a raw key each (ec_gcm_seal_messages / ec_gcm_open_messages) ----
-
-def _message_lists(what, bufs, lens, outs):
-    lens = [int(x) for x in lens]
-    bufs, outs = list(bufs), list(outs)
-    if len(bufs) != len(lens) or len(outs) != len(lens):
-        raise ValueError(f"one {what}, one length and one output per message")
-    if any(x < 0 for x in lens):
-        raise ValueError("a length is negative")
-    from .eestream import SegmentCodec as C
-    n = max(len(lens), 1)
-    c_in = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in bufs])
-    c_out = (ctypes.c_void_p * n)(*[0 if x is None else C._addr(x) for x in outs])
-    return len(lens), c_in, (ctypes.c_size_t * n)(*lens), c_out
-
 
 def seal_messages(scheme, plains, lens, dev_keys32, dev_nonces, outs, stream=None):
     """ec_gcm_seal_messages: message i is lens[i] plaintext bytes at plains[i]
@@ -271,10 +238,9 @@ def seal_messages(scheme, plains, lens, dev_keys32, dev_nonces, outs, stream=Non
     plaintext of an empty message); any alignment.  No prepared keys: the GPU
     derives everything from the key bytes.  `scheme` supplies the device and
     the staging.  Asynchronous on `stream`."""
-    from .eestream import SegmentCodec as C
-    nmsg, c_in, c_len, c_out = _message_lists("plaintext", plains, lens, outs)
-    rc = N.load().ec_gcm_seal_messages(scheme.ctx, nmsg, c_in, c_len, C._addr(dev_keys32), C._addr(dev_nonces), c_out,
-                                       C._stream(stream))
+    nmsg, c_in, c_len, c_out = _in_out_lists("plaintext", plains, "length", lens, outs, "message")
+    rc = N.load().ec_gcm_seal_messages(scheme.ctx, nmsg, c_in, c_len, B.addr(dev_keys32), B.addr(dev_nonces), c_out,
+                                       B.stream_handle(stream))
     _raise(scheme.ctx, rc)
 
 
@@ -283,10 +249,9 @@ def open_messages(scheme, ciphers, lens, dev_keys32, dev_nonces, outs, dev_statu
     (lens are plaintext lengths); dev_status is [nmsg] int32 on the device and
     dev_status[i] ends as 0, or as 1 when the tag did not verify -- outs[i] is
     then lens[i] zero bytes."""
-    from .eestream import SegmentCodec as C
-    nmsg, c_in, c_len, c_out = _message_lists("ciphertext", ciphers, lens, outs)
-    rc = N.load().ec_gcm_open_messages(scheme.ctx, nmsg, c_in, c_len, C._addr(dev_keys32), C._addr(dev_nonces), c_out,
-                                       C._addr(dev_status), C._stream(stream))
+    nmsg, c_in, c_len, c_out = _in_out_lists("ciphertext", ciphers, "length", lens, outs, "message")
+    rc = N.load().ec_gcm_open_messages(scheme.ctx, nmsg, c_in, c_len, B.addr(dev_keys32), B.addr(dev_nonces), c_out,
+                                       B.addr(dev_status), B.stream_handle(stream))
     _raise(scheme.ctx, rc)
 
 
@@ -386,4 +351,4 @@ def device_rows(rows, width: int, device=None):
         raise ValueError(f"expected {width} bytes per entry")
     host = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), width).copy()
     t = torch.from_numpy(host)
-    return t.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    return t.to(device if device is not None else B.default_device())

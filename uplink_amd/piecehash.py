@@ -29,11 +29,11 @@ EC_FLAG_HASH_PIECES, ec_encode_segments_host_hashed) hashes with BLAKE3 only.
 """
 from __future__ import annotations
 
-import ctypes
 import enum
 
 import numpy as np
 
+from . import _batch as B
 from . import _native as N
 from .eestream import _raise
 
@@ -82,11 +82,9 @@ def hash_device(base, npieces: int, piece_len: int, piece_stride: int, hashes, r
     or addresses): byte t of piece j at base + j*piece_stride +
     (t//run)*run_stride + t%run (run = 0: contiguous).  hashes: npieces*32
     device bytes."""
-    from .eestream import SegmentCodec
     L = N.load()
     call = L.ec_sha256_pieces if _sha(algo) else L.ec_blake3_pieces
-    rc = call(SegmentCodec._addr(base), npieces, piece_stride, piece_len, run, run_stride, SegmentCodec._addr(hashes),
-              SegmentCodec._stream(stream))
+    rc = call(B.addr(base), npieces, piece_stride, piece_len, run, run_stride, B.addr(hashes), B.stream_handle(stream))
     _raise(None, rc)
 
 
@@ -103,11 +101,10 @@ def hash_segments(scheme, segs, parity, nseg: int, nstripes: int, hashes, stream
     parity pieces from the EC_FLAG_PARITY_ONLY output.  hashes [nseg][n][32].
     SHA-256 goes through ec_sha256_segments_sized, with each segment's
     pointers computed from this uniform layout."""
-    from .eestream import SegmentCodec
     if _sha(algo):
         k, n, ess = scheme.required_count(), scheme.total_count(), scheme.erasure_share_size()
-        s0 = SegmentCodec._addr(segs)
-        p0 = SegmentCodec._addr(parity) if parity is not None else None
+        s0 = B.addr(segs)
+        p0 = B.addr(parity) if parity is not None else None
         if not s0 or (n > k and not p0):
             _raise(scheme.ctx, N.EC_ERR_INVALID_ARG)
         seg_bytes, par_bytes = nstripes * k * ess, nstripes * (n - k) * ess
@@ -115,14 +112,9 @@ def hash_segments(scheme, segs, parity, nseg: int, nstripes: int, hashes, stream
                             [p0 + g * par_bytes if p0 else None for g in range(nseg)], hashes, parity_only=True,
                             stream=stream, algo=algo)
         return
-    rc = N.load().ec_hash_segments(scheme.ctx, SegmentCodec._addr(segs),
-                                   SegmentCodec._addr(parity) if parity is not None else None, nseg, nstripes,
-                                   SegmentCodec._addr(hashes), SegmentCodec._stream(stream))
+    rc = N.load().ec_hash_segments(scheme.ctx, B.addr(segs), B.addr(parity) if parity is not None else None, nseg,
+                                   nstripes, B.addr(hashes), B.stream_handle(stream))
     _raise(scheme.ctx, rc)
-
-
-def _ctx_of(scheme_or_ctx):
-    return scheme_or_ctx.ctx if hasattr(scheme_or_ctx, "ctx") else scheme_or_ctx
 
 
 def hash_pieces_list(scheme_or_ctx, tensors, hashes=None, stream=None, algo=DEFAULT_ALGORITHM):
@@ -135,25 +127,23 @@ def hash_pieces_list(scheme_or_ctx, tensors, hashes=None, stream=None, algo=DEFA
     sha = _sha(algo)
     import torch
 
-    from .eestream import SegmentCodec
     tensors = list(tensors)
     for t in tensors:
         if t.dtype != torch.uint8 or not t.is_contiguous():
             raise ValueError("a piece is a contiguous uint8 tensor")
     npieces = len(tensors)
-    ts = stream if hasattr(stream, "cuda_stream") else None
     if hashes is None:
         dev = tensors[0].device if tensors else "cuda"
-        with torch.cuda.stream(ts) if ts is not None else _Null():
+        with B.stream_scope(stream):
             hashes = torch.empty((npieces, 32), dtype=torch.uint8, device=dev)
     elif hashes.numel() != npieces * 32 or hashes.dtype != torch.uint8 or not hashes.is_contiguous():
         raise ValueError("hashes is a contiguous uint8 tensor of npieces*32 bytes")
-    ctx = _ctx_of(scheme_or_ctx)
-    c_ptrs = (ctypes.c_void_p * max(npieces, 1))(*[t.data_ptr() if t.numel() else None for t in tensors])
-    c_lens = (ctypes.c_size_t * max(npieces, 1))(*[t.numel() for t in tensors])
+    ctx = B.ctx_of(scheme_or_ctx)
     L = N.load()
     call = L.ec_sha256_pieces_list if sha else L.ec_blake3_pieces_list
-    rc = call(ctx, npieces, c_ptrs, c_lens, hashes.data_ptr() if npieces else None, SegmentCodec._stream(stream))
+    rc = call(ctx, npieces, B.ptr_array([t if t.numel() else None for t in tensors]),
+              B.size_array([t.numel() for t in tensors]), hashes.data_ptr() if npieces else None,
+              B.stream_handle(stream))
     _raise(ctx, rc)
     return hashes
 
@@ -172,32 +162,17 @@ def hash_segments_sized(scheme_or_ctx, segs, nstripes, pieces, hashes, parity_on
     be None.  nstripes[g] == 0 skips segment g (its buffers may be None, its hash
     rows stay as they are).  Asynchronous on `stream`."""
     sha = _sha(algo)
-    from .eestream import SegmentCodec
-    nstripes = [int(x) for x in nstripes]
+    nstripes, pieces = list(nstripes), list(pieces)
     nseg = len(nstripes)
-    pieces = list(pieces)
     segs = None if segs is None else list(segs)
     if len(pieces) != nseg or (segs is not None and len(segs) != nseg):
         raise ValueError("one segment, one stripe count and one piece buffer per segment")
-    if any(x < 0 for x in nstripes):
-        raise ValueError("a stripe count is negative")
+    c_nst = B.size_array(nstripes, nseg, "stripe count")
     if parity_only and segs is None:
         raise ValueError("parity_only reads the data pieces from the segments")
-
-    def arr(xs):
-        return (ctypes.c_void_p * max(nseg, 1))(*[None if x is None else SegmentCodec._addr(x) for x in xs])
-
-    ctx = _ctx_of(scheme_or_ctx)
+    ctx = B.ctx_of(scheme_or_ctx)
     L = N.load()
     call = L.ec_sha256_segments_sized if sha else L.ec_hash_segments_sized
-    rc = call(ctx, nseg, None if segs is None else arr(segs), (ctypes.c_size_t * max(nseg, 1))(*nstripes), arr(pieces),
-              N.EC_FLAG_PARITY_ONLY if parity_only else 0, SegmentCodec._addr(hashes), SegmentCodec._stream(stream))
+    rc = call(ctx, nseg, None if segs is None else B.ptr_array(segs), c_nst, B.ptr_array(pieces),
+              N.EC_FLAG_PARITY_ONLY if parity_only else 0, B.addr(hashes), B.stream_handle(stream))
     _raise(ctx, rc)
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False

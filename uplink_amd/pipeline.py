@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _batch as B
 from . import _native as N
 from .eestream import SegmentCodec, _raise
 from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, prepare_keys
@@ -75,8 +76,7 @@ class DevicePipeline:
     def upload(self, plain, nseg: int, dev_keys, dev_nonces, enc, pieces, hashes, stream=None):
         """plain [nseg][plain_cap] holds plain_len bytes per segment (the rest
         is overwritten with padding).  Fills enc, pieces and hashes."""
-        g, L, s = self.g, self._lib, SegmentCodec._stream(stream)
-        a = SegmentCodec._addr
+        g, L, s, a = self.g, self._lib, B.stream_handle(stream), B.addr
         _raise(None, L.ec_pad_segments(a(plain), nseg, g.plain_cap, g.plain_len, g.in_block, s))
         _raise(None, L.ec_gcm_seal_segments_strided(a(plain), g.plain_cap, nseg, g.nblocks, g.in_block, a(dev_keys),
                                                     a(dev_nonces), a(enc), g.padded_len, s))
@@ -91,8 +91,7 @@ class DevicePipeline:
         into plain_out [nseg][plain_cap]; dev_status[g] = -1 or the first
         block of segment g that failed authentication.  The plaintext of a
         segment is plain_out[g, :plain_len]."""
-        g, L, s = self.g, self._lib, SegmentCodec._stream(stream)
-        a = SegmentCodec._addr
+        g, L, s, a = self.g, self._lib, B.stream_handle(stream), B.addr
         n = pieces.shape[1]
         base = a(pieces)
         self.codec.rebuild_segments(list(nums), [base + i * g.piece_len for i in nums], g.nstripes, enc, nseg=nseg,

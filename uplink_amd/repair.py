@@ -22,47 +22,89 @@ segments in one stream-ordered pass.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Iterable, List, Sequence
 
+from . import _batch as B
 from . import _native as N
-from .eestream import NotEnoughShares, SegmentCodec, _raise
+from .eestream import NotEnoughShares, _raise
 
 
-def _ctx_of(scheme_or_ctx):
-    return scheme_or_ctx.ctx if hasattr(scheme_or_ctx, "ctx") else scheme_or_ctx
-
-
-def _flatten(segments):
-    """(nshares, nums, piece addresses, ntargets, targets) of a batch, as the C call takes them."""
+def _call_args(segments, out_ptrs):
+    """(nseg, nshares[], nums[], pieces[], ntargets[], targets[], outputs[]) of a batch, as both C calls take them"""
     nsh, nums, ptrs, ntg, tgts = [], [], [], [], []
     for snums, pieces, targets in segments:
         snums, pieces, targets = list(snums), list(pieces), list(targets)
         if len(snums) != len(pieces):
             raise ValueError("nums and pieces differ in length")
         nsh.append(len(snums))
-        nums += [int(x) for x in snums]
-        ptrs += [SegmentCodec._addr(p) for p in pieces]
+        nums += snums
+        ptrs += pieces
         ntg.append(len(targets))
-        tgts += [int(t) for t in targets]
-    return nsh, nums, ptrs, ntg, tgts
-
-
-def _carr(ctype, values):
-    return (ctype * max(len(values), 1))(*values)
+        tgts += targets
+    return (len(nsh), B.int_array(nsh), B.int_array(nums), B.ptr_array(ptrs), B.int_array(ntg), B.int_array(tgts),
+            B.ptr_array(out_ptrs, len(tgts), "output", "target"))
 
 
 def repair_call(ctx, segments, out_ptrs: Sequence[int], nstripes: int, flags: int = 0, status=None, stream=None) -> int:
     """ec_repair_segments_sets on raw arguments; returns its code.  segments:
     (nums, pieces, targets) each, pieces and out_ptrs device tensors or addresses."""
-    nsh, nums, ptrs, ntg, tgts = _flatten(segments)
-    out_ptrs = [SegmentCodec._addr(p) for p in out_ptrs]
-    if len(out_ptrs) != len(tgts):
-        raise ValueError("one output per target")
-    return N.load().ec_repair_segments_sets(
-        ctx, len(nsh), _carr(ctypes.c_int, nsh), _carr(ctypes.c_int, nums), _carr(ctypes.c_void_p, ptrs),
-        _carr(ctypes.c_int, ntg), _carr(ctypes.c_int, tgts), _carr(ctypes.c_void_p, out_ptrs), nstripes, flags,
-        SegmentCodec._addr(status) if status is not None else None, SegmentCodec._stream(stream))
+    return N.load().ec_repair_segments_sets(ctx, *_call_args(segments, out_ptrs), nstripes, flags,
+                                            None if status is None else B.addr(status), B.stream_handle(stream))
+
+
+def repair_call_sized(ctx, segments, out_ptrs: Sequence[int], nstripes_list: Sequence[int], flags: int = 0, status=None,
+                      stream=None) -> int:
+    """ec_repair_segments_sized on raw arguments; returns its code.  As
+    repair_call with a stripe count per segment."""
+    args = _call_args(segments, out_ptrs)
+    return N.load().ec_repair_segments_sized(ctx, *args, B.size_array(nstripes_list, args[0], "stripe count"), flags,
+                                             None if status is None else B.addr(status), B.stream_handle(stream))
+
+
+def _repair(ctx, call, segments, plens, ess, k, check, hash_pieces, hash_algo, stream):
+    """The repair of a validated batch, behind both public forms: plens[g] is
+    the piece length of segment g (a multiple of ess) and call(segments, rows,
+    stripe counts, flags, status) the raw call over the batch or a part of it."""
+    import torch
+
+    dev = next((p.device for _, pieces, _ in segments for p in pieces), None)
+    if dev is None:  # nothing to repair from
+        return ([], []) if hash_pieces else []
+    stripes = [p // ess for p in plens]
+    flags = N.EC_FLAG_CHECK_SHARES if check else 0
+    with B.stream_scope(stream):
+        # one allocation per segment: each is 16-byte aligned, so each stays in the pass
+        outs = [torch.empty((len(t), p), dtype=torch.uint8, device=dev) for (_, _, t), p in zip(segments, plens)]
+        rows = [o[i] for o in outs for i in range(o.shape[0])]
+        status = torch.empty(len(segments), dtype=torch.int32, device=dev) if check else None
+        _raise(ctx, call(segments, rows, stripes, flags, status))
+        bad = [g for g, s in enumerate(B.read_back(status, stream)) if s] if check else []
+        if bad:
+            # a flagged segment is corrected as Decode corrects it, its pieces rewritten in place, with
+            # its own stripe count (the scratch takes the largest); then those segments are repaired again
+            scratch = torch.empty(max(plens[g] for g in bad) * k, dtype=torch.uint8, device=dev)
+            for g in bad:
+                nums, pieces, _ = segments[g]
+                rc = N.load().ec_decode_segments(ctx, len(nums), B.int_array(nums), B.ptr_array(pieces), stripes[g],
+                                                 scratch.data_ptr(), B.stream_handle(stream))
+                _raise(ctx, rc)
+            again = torch.empty(len(bad), dtype=torch.int32, device=dev)
+            rows2 = [outs[g][i] for g in bad for i in range(outs[g].shape[0])]
+            _raise(ctx, call([segments[g] for g in bad], rows2, [stripes[g] for g in bad], flags, again))
+            if any(B.read_back(again, stream)):  # (corrected shares are codewords: not expected)
+                _raise(ctx, N.EC_ERR_TOO_MANY_ERRORS)
+        if not hash_pieces:
+            return outs
+        # every regenerated row of the batch in one list call, a length per piece
+        from .piecehash import DEFAULT_ALGORITHM, hash_pieces_list
+        algo = DEFAULT_ALGORITHM if hash_algo is None else hash_algo
+        flat = hash_pieces_list(ctx, rows, stream=stream, algo=algo) if rows else None
+        hashes, at = [], 0
+        for o in outs:
+            cnt = o.shape[0]
+            hashes.append(flat[at:at + cnt] if cnt else torch.empty((0, 32), dtype=torch.uint8, device=dev))
+            at += cnt
+        return outs, hashes
 
 
 def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces: bool = False, hash_algo=None,
@@ -82,90 +124,23 @@ def repair_segments(scheme_or_ctx, segments, *, check: bool = False, hash_pieces
     NotEnoughShares are raised as eestream words them.  With check the call
     returns after the status has been read; without it, it is asynchronous on
     `stream`."""
-    import torch
-
-    ctx = _ctx_of(scheme_or_ctx)
+    ctx = B.ctx_of(scheme_or_ctx)
     lib = N.load()
     segments = [(list(a), list(b), list(c)) for a, b, c in segments]
-    ess = lib.ec_share_size(ctx)
-    k = lib.ec_required(ctx)
+    ess, k = lib.ec_share_size(ctx), lib.ec_required(ctx)
     if ess <= 0 or k <= 0:
         _raise(None, N.EC_ERR_INVALID_ARG)
-    plen = None
-    for _, pieces, _ in segments:
-        for p in pieces:
-            if plen is None:
-                plen = p.numel()
-            elif p.numel() != plen:
-                _raise(ctx, N.EC_ERR_SHARE_SIZE)
-    if plen is None:
-        return ([], []) if hash_pieces else []
+    lens = {p.numel() for _, pieces, _ in segments for p in pieces}
+    if len(lens) > 1:  # one piece length for the whole batch
+        _raise(ctx, N.EC_ERR_SHARE_SIZE)
+    plen = lens.pop() if lens else 0
     if plen % ess:
         _raise(ctx, N.EC_ERR_INVALID_ARG)
-    nstripes = plen // ess
-    dev = segments[0][1][0].device
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
-        outs = [torch.empty((len(t), plen), dtype=torch.uint8, device=dev) for _, _, t in segments]
-        rows = [o[i] for o in outs for i in range(o.shape[0])]
-        status = torch.empty(len(segments), dtype=torch.int32, device=dev) if check else None
-        flags = N.EC_FLAG_CHECK_SHARES if check else 0
-        _raise(ctx, repair_call(ctx, segments, rows, nstripes, flags, status, stream))
 
-        def read(t):  # (waits for the stream; a raw stream handle is not one torch's copy follows)
-            if stream is not None and ts is None:
-                torch.cuda.synchronize()
-            return t.cpu().tolist()
+    def call(segs, rows, stripes, flags, status):
+        return repair_call(ctx, segs, rows, plen // ess, flags, status, stream)
 
-        if check:
-            bad = [g for g, s in enumerate(read(status)) if s]
-            if bad:
-                scratch = torch.empty(nstripes * k * ess, dtype=torch.uint8, device=dev)
-                st = SegmentCodec._stream(stream)
-                for g in bad:
-                    nums, pieces, _ = segments[g]
-                    rc = lib.ec_decode_segments(ctx, len(nums), _carr(ctypes.c_int, nums),
-                                                _carr(ctypes.c_void_p, [p.data_ptr() for p in pieces]), nstripes,
-                                                scratch.data_ptr(), st)
-                    _raise(ctx, rc)
-                again = [segments[g] for g in bad]
-                st2 = torch.empty(len(bad), dtype=torch.int32, device=dev)
-                rows2 = [outs[g][i] for g in bad for i in range(outs[g].shape[0])]
-                _raise(ctx, repair_call(ctx, again, rows2, nstripes, flags, st2, stream))
-                if any(read(st2)):  # (corrected shares are codewords: not expected)
-                    _raise(ctx, N.EC_ERR_TOO_MANY_ERRORS)
-        if not hash_pieces:
-            return outs
-        # every regenerated row in one list call: they have one length and differ in where they lie
-        from .piecehash import DEFAULT_ALGORITHM, hash_pieces_list
-        algo = DEFAULT_ALGORITHM if hash_algo is None else hash_algo
-        flat = hash_pieces_list(ctx, rows, stream=stream, algo=algo) if rows else None
-        hashes, at = [], 0
-        for o in outs:
-            cnt = o.shape[0]
-            hashes.append(flat[at:at + cnt] if cnt else torch.empty((0, 32), dtype=torch.uint8, device=dev))
-            at += cnt
-        return outs, hashes
-
-
-def repair_call_sized(ctx, segments, out_ptrs: Sequence[int], nstripes_list: Sequence[int], flags: int = 0, status=None,
-                      stream=None) -> int:
-    """ec_repair_segments_sized on raw arguments; returns its code.  As
-    repair_call with a stripe count per segment."""
-    nsh, nums, ptrs, ntg, tgts = _flatten(segments)
-    out_ptrs = [SegmentCodec._addr(p) for p in out_ptrs]
-    if len(out_ptrs) != len(tgts):
-        raise ValueError("one output per target")
-    nstripes_list = [int(x) for x in nstripes_list]
-    if len(nstripes_list) != len(nsh):
-        raise ValueError("one stripe count per segment")
-    if any(x < 0 for x in nstripes_list):
-        raise ValueError("a negative stripe count")
-    return N.load().ec_repair_segments_sized(
-        ctx, len(nsh), _carr(ctypes.c_int, nsh), _carr(ctypes.c_int, nums), _carr(ctypes.c_void_p, ptrs),
-        _carr(ctypes.c_int, ntg), _carr(ctypes.c_int, tgts), _carr(ctypes.c_void_p, out_ptrs),
-        _carr(ctypes.c_size_t, nstripes_list), flags, SegmentCodec._addr(status) if status is not None else None,
-        SegmentCodec._stream(stream))
+    return _repair(ctx, call, segments, [plen] * len(segments), ess, k, check, hash_pieces, hash_algo, stream)
 
 
 def _sizes_of(scheme_or_ctx, ctx):
@@ -190,79 +165,24 @@ def repair_segments_sized(scheme_or_ctx, segments, *, check: bool = False, hash_
 
     check: as repair_segments; flagged segments are corrected through Decode
     with their own stripe count and repaired again in one sized call."""
-    import torch
-
-    ctx = _ctx_of(scheme_or_ctx)
+    ctx = B.ctx_of(scheme_or_ctx)
     segments = [(list(a), list(b), list(c)) for a, b, c in segments]
     ess, k = _sizes_of(scheme_or_ctx, ctx)
     if ess <= 0 or k <= 0:
         _raise(None, N.EC_ERR_INVALID_ARG)
-    plens, dev = [], None
+    plens = []
     for _, pieces, _ in segments:
         plen = pieces[0].numel() if pieces else 0
-        for p in pieces:
-            if p.numel() != plen:
-                _raise(ctx, N.EC_ERR_SHARE_SIZE)
+        if any(p.numel() != plen for p in pieces):
+            _raise(ctx, N.EC_ERR_SHARE_SIZE)
         if plen % ess:
             _raise(ctx, N.EC_ERR_INVALID_ARG)
-        if pieces and dev is None:
-            dev = pieces[0].device
         plens.append(plen)
-    if dev is None:
-        return ([], []) if hash_pieces else []
-    lib = N.load()
-    stripes = [p // ess for p in plens]
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
-        # one allocation per segment: each is 16-byte aligned, so each stays in the pass
-        outs = [torch.empty((len(t), p), dtype=torch.uint8, device=dev) for (_, _, t), p in zip(segments, plens)]
-        rows = [o[i] for o in outs for i in range(o.shape[0])]
-        status = torch.empty(len(segments), dtype=torch.int32, device=dev) if check else None
-        flags = N.EC_FLAG_CHECK_SHARES if check else 0
-        _raise(ctx, repair_call_sized(ctx, segments, rows, stripes, flags, status, stream))
 
-        def read(t):  # (waits for the stream; a raw stream handle is not one torch's copy follows)
-            if stream is not None and ts is None:
-                torch.cuda.synchronize()
-            return t.cpu().tolist()
+    def call(segs, rows, stripes, flags, status):
+        return repair_call_sized(ctx, segs, rows, stripes, flags, status, stream)
 
-        if check:
-            bad = [g for g, s in enumerate(read(status)) if s]
-            if bad:
-                scratch = torch.empty(max(plens[g] for g in bad) * k, dtype=torch.uint8, device=dev)
-                st = SegmentCodec._stream(stream)
-                for g in bad:
-                    nums, pieces, _ = segments[g]
-                    rc = lib.ec_decode_segments(ctx, len(nums), _carr(ctypes.c_int, nums),
-                                                _carr(ctypes.c_void_p, [p.data_ptr() for p in pieces]), stripes[g],
-                                                scratch.data_ptr(), st)
-                    _raise(ctx, rc)
-                again = [segments[g] for g in bad]
-                st2 = torch.empty(len(bad), dtype=torch.int32, device=dev)
-                rows2 = [outs[g][i] for g in bad for i in range(outs[g].shape[0])]
-                _raise(ctx, repair_call_sized(ctx, again, rows2, [stripes[g] for g in bad], flags, st2, stream))
-                if any(read(st2)):  # (corrected shares are codewords: not expected)
-                    _raise(ctx, N.EC_ERR_TOO_MANY_ERRORS)
-        if not hash_pieces:
-            return outs
-        # every regenerated row of the batch in one list call, a length per piece
-        from .piecehash import DEFAULT_ALGORITHM, hash_pieces_list
-        algo = DEFAULT_ALGORITHM if hash_algo is None else hash_algo
-        flat = hash_pieces_list(ctx, rows, stream=stream, algo=algo) if rows else None
-        hashes, at = [], 0
-        for o in outs:
-            cnt = o.shape[0]
-            hashes.append(flat[at:at + cnt] if cnt else torch.empty((0, 32), dtype=torch.uint8, device=dev))
-            at += cnt
-        return outs, hashes
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+    return _repair(ctx, call, segments, plens, ess, k, check, hash_pieces, hash_algo, stream)
 
 
 class SegmentRepairer:

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 from typing import Sequence, Tuple
 
+from . import _batch as B
 from .eestream import SegmentCodec
 from .encryption import DEFAULT_BLOCK_SIZE, TAG_SIZE, device_rows, seal_messages, seal_segments_sized
 
@@ -36,6 +37,15 @@ def upload_geometry(size: int, es) -> Tuple[int, int, int]:
     stripe = es.stripe_size()
     padded = size + 4 + (stripe - (size + 4) % stripe) % stripe
     return padded, padded // es.required_count(), padded // stripe
+
+
+def _check_buffer(size: int, buf, need: int):
+    """an upload's buffer: a contiguous uint8 tensor of at least `need` bytes"""
+    import torch
+    if buf.dtype != torch.uint8 or not buf.is_contiguous():
+        raise ValueError("an upload's buffer is a contiguous uint8 tensor")
+    if buf.numel() < need:
+        raise ValueError(f"an upload of {size} bytes needs a buffer of {need} bytes, got {buf.numel()}")
 
 
 def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only: bool = False,
@@ -59,13 +69,9 @@ def encode_uploads(scheme, uploads: Sequence[Tuple[int, object]], *, parity_only
     geo = []
     for size, buf in uploads:
         padded, piece_size, ns = upload_geometry(int(size), scheme)
-        if buf.dtype != torch.uint8 or not buf.is_contiguous():
-            raise ValueError("an upload's buffer is a contiguous uint8 tensor")
-        if buf.numel() < padded:
-            raise ValueError(f"an upload of {int(size)} bytes needs a buffer of {padded} bytes, got {buf.numel()}")
+        _check_buffer(int(size), buf, padded)
         geo.append((int(size), piece_size, ns, buf))
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    with B.stream_scope(stream):
         # one allocation per upload: each is 16-byte aligned, so every segment stays in the pass
         outs = [torch.empty((rows, piece_size), dtype=torch.uint8, device=buf.device) for _, piece_size, _, buf in geo]
         codec.encode_segments_sized([g[3] for g in geo], [g[2] for g in geo], outs, data_len=[g[0] for g in geo],
@@ -113,13 +119,9 @@ def seal_uploads(scheme, uploads: Sequence[Tuple[int, object]], dev_keys, dev_no
     geo = []
     for size, buf in uploads:
         nblocks, plain_cap, enc_len = cipher_geometry(int(size), block_size)
-        if buf.dtype != torch.uint8 or not buf.is_contiguous():
-            raise ValueError("an upload's buffer is a contiguous uint8 tensor")
-        if buf.numel() < plain_cap:
-            raise ValueError(f"an upload of {int(size)} bytes needs a buffer of {plain_cap} bytes, got {buf.numel()}")
+        _check_buffer(int(size), buf, plain_cap)
         geo.append((int(size), nblocks, enc_len, buf))
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    with B.stream_scope(stream):
         # one allocation per upload: each is 16-byte aligned
         encs = [torch.empty(upload_geometry(enc_len, scheme)[0], dtype=torch.uint8, device=buf.device)
                 for _, _, enc_len, buf in geo]
@@ -150,9 +152,8 @@ def seal_inline_uploads(scheme, uploads: Sequence[object], content_keys, nonces,
     for buf in uploads:
         if buf.dtype != torch.uint8 or not buf.is_contiguous():
             raise ValueError("an upload's plaintext is a contiguous uint8 tensor")
-    dev = uploads[0].device if uploads else torch.device("cuda", torch.cuda.current_device())
-    ts = stream if hasattr(stream, "cuda_stream") else None
-    with torch.cuda.stream(ts) if ts is not None else _Null():
+    dev = uploads[0].device if uploads else B.default_device()
+    with B.stream_scope(stream):
         ck, dk = device_rows(content_keys, 32, dev), device_rows(derived_keys, 32, dev)
         nn, kn = device_rows(nonces, 12, dev), device_rows(key_nonces, 12, dev)
         if not (len(ck) == len(dk) == len(nn) == len(kn) == n):
@@ -173,14 +174,5 @@ def seal_inline_uploads(scheme, uploads: Sequence[object], content_keys, nonces,
         seal_messages(scheme, plains, lens, keys32, nonces12, outs, stream=stream)
         # keys32 and nonces12 are read by the queued kernels: freed on this stream they are reused only
         # behind them; a raw stream handle is not the stream they were made on, so wait for it
-        if stream is not None and ts is None:
-            torch.cuda.synchronize()
+        B.wait_if_raw(stream)
     return encs, enc_keys
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
